@@ -11,6 +11,10 @@ progressive search (threshold 0.1, max_candidates_per_level 20 as HilbertQuantiz
 1M-frame corpus per GPU (config 3; config 4 = 1M per GPU x N GPUs with the RCCL all-gather merge).
 
 Launch: python bench.py [--gpus N --steps K --warmup W]; N > 1 under torch.distributed.run.
+A plain run times the headline only: set-up, W warm-up steps, K timed steps, one JSON line.  --full adds every
+other leg (pre-computed index, search, frames, ingest, API latency, stream, CPU baselines) to the same line.
+--dump-outputs DIR writes the headline's outputs of the last timed step (a fixed row sample) as DIR/<name>.npy;
+the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -75,7 +79,40 @@ def parse():
                     help="module:attribute=value (int, or str where the attribute is one; attribute may be Class.attr): "
                          "a host-side variant, e.g. hq_mi355x.kernels:FINAL_LEVEL0_LISTS=1 "
                          "(A/B runs only)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every other leg (pre-computed index, search, frames, ingest, API, "
+                         "stream, CPU baselines; the --no-* options drop single legs); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the headline's last timed step computed to DIR/<name>.npy (a fixed row sample "
+                         "when the batch is larger)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        for leg in FULL_LEGS:
+            setattr(args, "no_" + leg, True)
+    return args
+
+
+# legs that only a --full run measures (each with its own --no-<leg> option)
+FULL_LEGS = ("search", "stream", "precomputed", "ingest", "frames", "api", "cpu")
+DUMP_ROWS = 2048  # rows of the headline's outputs --dump-outputs keeps: 2048 x (65 x 64 + 64 + 2) values, ~35 MB
+
+
+def dump_outputs(path, frames, idx, mm):
+    """--dump-outputs: the tensors quantize_batch returned in the last timed step (frames u8 -> float32, exact;
+    indices float64; minmax float32) as <name>.npy.  Batches above DUMP_ROWS rows are cut to a fixed sample:
+    the first and the last row and a seeded draw of the others, in row order."""
+    N = int(frames.shape[0])
+    if N > DUMP_ROWS:
+        rows = np.random.default_rng(0).choice(np.arange(1, N - 1), DUMP_ROWS - 2, replace=False)
+        rows = np.sort(np.concatenate([[0, N - 1], rows]))
+    else:
+        rows = np.arange(N)
+    sel = torch.from_numpy(rows).to(frames.device)
+    os.makedirs(path, exist_ok=True)
+    for name, t, dt in (("frames", frames, np.float32), ("indices", idx, np.float64), ("minmax", mm, np.float32)):
+        np.save(os.path.join(path, name + ".npy"), t.index_select(0, sel).cpu().numpy().astype(dt))
 
 
 def dist_setup(args):
@@ -829,10 +866,15 @@ def main():
     mm = torch.empty((N, 2), dtype=torch.float32, device=dev)
     out = (frames, idx, mm)
 
+    got = [None]  # what the last step's caller received
+
     def step():
-        quantize_batch(X, min_efficiency_ratio=0.2, index_space_size=L, out=out)
+        got[0] = quantize_batch(X, min_efficiency_ratio=0.2, index_space_size=L, out=out)
 
     wall, kern = timed(step, args.steps, args.warmup, world)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *got[0])
+    got[0] = None
     ms = wall / args.steps * 1e3
     value = N * world * args.steps / wall
     bytes_per_emb = 4 * d + (n + 1) * n + 8 * L + 8

@@ -214,3 +214,51 @@ def test_bench_traffic_table_well_formed():
     for n in names:
         v = mod.load_traffic(n)
         assert isinstance(v, float) and v > 0, (n, v)
+
+
+def test_bench_plain_run_and_output_dump(tmp_path, monkeypatch):
+    """bench.py's option logic without a GPU: a plain run switches every leg but the headline off, --full leaves
+    them on (minus the --no-* ones), --steps 0 is refused; --dump-outputs writes float32 / float64 .npy files of
+    the same fixed row sample on every call, the whole batch when it is small, well under 64 MB."""
+    import importlib.util
+    import sys
+    import torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("_bench_mod2", os.path.join(root, "bench.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+
+    def parse(*argv):
+        monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+        return mod.parse()
+
+    a = parse("--gpus", "1", "--steps", "7", "--warmup", "2")
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    assert all(getattr(a, "no_" + leg) for leg in mod.FULL_LEGS)
+    a = parse("--full", "--no-stream", "--dump-outputs", "d")
+    assert a.full and a.dump_outputs == "d"
+    assert [leg for leg in mod.FULL_LEGS if getattr(a, "no_" + leg)] == ["stream"]
+    with pytest.raises(SystemExit):
+        parse("--steps", "0")
+
+    N = mod.DUMP_ROWS + 1000
+    g = torch.Generator().manual_seed(0)
+    frames = torch.randint(0, 256, (N, 5, 4), generator=g, dtype=torch.uint8)
+    idx = torch.randn((N, 4), generator=g, dtype=torch.float64)
+    mm = torch.randn((N, 2), generator=g, dtype=torch.float32)
+    got = []
+    for d in ("a", "b"):
+        mod.dump_outputs(str(tmp_path / d), frames, idx, mm)
+        got.append({n: np.load(tmp_path / d / f"{n}.npy") for n in ("frames", "indices", "minmax")})
+    for n, dt in (("frames", np.float32), ("indices", np.float64), ("minmax", np.float32)):
+        assert got[0][n].dtype == dt and len(got[0][n]) == mod.DUMP_ROWS
+        assert got[0][n].tobytes() == got[1][n].tobytes()
+    # the sample is rows of the tensors, first and last among them, in row order
+    rows = [int(np.flatnonzero((idx.numpy() == r).all(1))[0]) for r in got[0]["indices"]]
+    assert rows[0] == 0 and rows[-1] == N - 1 and rows == sorted(set(rows))
+    assert np.array_equal(got[0]["frames"], frames.numpy()[rows].astype(np.float32))
+    assert np.array_equal(got[0]["minmax"], mm.numpy()[rows])
+    # the headline's row (65 x 64 frame, 64 indices, min / max) at DUMP_ROWS rows stays under the 64 MB limit
+    assert mod.DUMP_ROWS * (65 * 64 * 4 + 64 * 8 + 2 * 4) <= 64 * 2 ** 20
+    mod.dump_outputs(str(tmp_path / "s"), frames[:10], idx[:10], mm[:10])
+    assert np.array_equal(np.load(tmp_path / "s" / "indices.npy"), idx[:10].numpy())

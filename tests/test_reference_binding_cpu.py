@@ -1,14 +1,12 @@
 """The drop-in joins the reference's type hierarchy when the reference package is importable (SURVEY §7
 step 3, VERDICT r02 missing item 7): exceptions subclass the reference's, components subclass its ABCs
 (interfaces.py:12-225) and the data model is its own dataclasses (models.py:11-80).  Checked in child
-processes: with a minimal stand-in package named hilbert_quantization (always), with the real reference
-when it is present in this container (skipped elsewhere), and without any (own types)."""
+processes: with a minimal stand-in package named hilbert_quantization (the reference's class and field
+names, none of its code), and without any (own types)."""
 import os
 import subprocess
 import sys
 import textwrap
-
-import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "hilbert-quantization_amd")
@@ -145,15 +143,6 @@ def test_binds_to_stand_in_reference(tmp_path):
     for name, text in STAND_IN.items():
         (pkg / name).write_text(text)
     r = _run(CHECK, str(tmp_path))
-    assert r.returncode == 0 and "bound" in r.stdout, r.stderr[-3000:]
-
-
-def test_binds_to_real_reference_when_present(tmp_path):
-    ref = "/root/reference"
-    if not os.path.isdir(os.path.join(ref, "hilbert_quantization")):
-        pytest.skip("reference tree not present (GPU box)")
-    (tmp_path / "cv2.py").write_text("# inert stub: the reference imports cv2 at package import\n")
-    r = _run("import logging; logging.disable(logging.CRITICAL)\n" + CHECK, os.pathsep.join([str(tmp_path), ref]))
     assert r.returncode == 0 and "bound" in r.stdout, r.stderr[-3000:]
 
 

@@ -4,7 +4,7 @@
 # (results: gpurun_out/<tag>_*.json; a variant library is loaded through HQ_LIB_VARIANT)
 O=$GRAFT_REPO_ROOT/gpurun_out
 tag=$1; shift
-B="--corpus-total 0 --no-cpu --no-stream --no-precomputed --no-ingest --no-frames --no-hard --no-api --steps 3 --warmup 1"
+B="--full --corpus-total 0 --no-cpu --no-stream --no-precomputed --no-ingest --no-frames --no-hard --no-api --steps 3 --warmup 1"
 i=0
 for rep in 1 2; do
 for v in "$@"; do

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Run bench.py with Python-level settings applied first (A/B of host-side variants within one call).
-usage: ab_py.py "<python statements>" [bench args...]   e.g. ab_py.py "IndexCorpus._count_read = 'copy'" --no-cpu"""
+usage: ab_py.py "<python statements>" [bench args...]   e.g. ab_py.py "IndexCorpus._count_read = 'copy'" --full --no-cpu"""
 import os
 import runpy
 import sys

@@ -8,7 +8,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 run() {  # name, counters...
   local name=$1; shift
-  timeout -k 10 300 rocprofv3 --pmc "$@" -d $OUT/$name -o $name --output-format csv -- python bench.py --steps 3 --warmup 1 --no-cpu "${BENCH_ARGS[@]}" > $OUT/$name.log 2>&1
+  timeout -k 10 300 rocprofv3 --pmc "$@" -d $OUT/$name -o $name --output-format csv -- python bench.py --full --steps 3 --warmup 1 --no-cpu "${BENCH_ARGS[@]}" > $OUT/$name.log 2>&1
   local rc=$?; echo "$name rc=$rc"; return $rc
 }
 BENCH_ARGS=("$@")

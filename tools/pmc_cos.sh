@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 for v in "$@"; do export "$v"; done
 run() {
   local name=$1; shift
-  timeout -k 10 -s KILL 120 rocprofv3 --pmc "$@" -d $OUT/$name -o $name --output-format csv -- python bench.py --steps 1 --warmup 0 --no-cpu --no-search --no-stream --no-precomputed --no-ingest > $OUT/$name.log 2>&1
+  timeout -k 10 -s KILL 120 rocprofv3 --pmc "$@" -d $OUT/$name -o $name --output-format csv -- python bench.py --full --steps 1 --warmup 0 --no-cpu --no-search --no-stream --no-precomputed --no-ingest > $OUT/$name.log 2>&1
   local rc=$?; echo "$name rc=$rc"; return $rc
 }
 run sq SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_LDS && \

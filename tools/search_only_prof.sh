@@ -6,7 +6,7 @@ TAG=${1:-s}
 OUT=gpurun_out
 mkdir -p $OUT
 export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/sprof_$TAG -o run --output-format csv -- python3 bench.py --steps 2 --warmup 1 --n-emb 10000 --no-cpu --no-stream --no-precomputed --no-ingest --no-frames --search-steps 20 > $OUT/sprof_$TAG.log 2>&1; rc=$?
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/sprof_$TAG -o run --output-format csv -- python3 bench.py --full --steps 2 --warmup 1 --n-emb 10000 --no-cpu --no-stream --no-precomputed --no-ingest --no-frames --search-steps 20 > $OUT/sprof_$TAG.log 2>&1; rc=$?
 echo "rocprof rc=$rc"
 [ $rc -eq 0 ] || exit $rc
 python3 - "$OUT/sprof_$TAG" <<'PY'

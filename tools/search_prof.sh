@@ -9,7 +9,7 @@ timeout -k 10 400 python -m pytest tests/test_gpu_search.py -q -rf -x > $OUT/t_s
 tail -3 $OUT/t_search_$TAG.log
 [ $rc -le 1 ] || exit $rc
 export TMPDIR=/tmp
-timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/prof_$TAG -o run --output-format csv -- python bench.py --steps 5 --warmup 1 --no-cpu --n-emb 100000 > $OUT/prof_$TAG.log 2>&1; rc=$?
+timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/prof_$TAG -o run --output-format csv -- python bench.py --full --steps 5 --warmup 1 --no-cpu --n-emb 100000 > $OUT/prof_$TAG.log 2>&1; rc=$?
 echo "rocprof rc=$rc"
 python3 - "$OUT/prof_$TAG" <<'PY'
 import csv, glob, json, sys
