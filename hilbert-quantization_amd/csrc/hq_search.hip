@@ -100,8 +100,8 @@ constexpr int kAuxF32 = 1, kAuxUnsafe = 2;
 __device__ __forceinline__ int aux_bits(const double* st) { return (int)st[3]; }
 
 // one (row, segment): x = the row's raw values (global memory or an LDS copy of the row)
-__device__ __forceinline__ void seg_prepare_one(const double* xrow, int64_t row, int s, const SegInfo& si,
-                                                int all_f32, const uint8_t* __restrict__ row_f32,
+// (is32: the row is a float32 source)
+__device__ __forceinline__ void seg_prepare_one(const double* xrow, int64_t row, int s, const SegInfo& si, bool is32,
                                                 double* __restrict__ Z, double* __restrict__ stats) {
   const double* x = xrow + si.src[s];
   const int m = si.len[s];
@@ -113,7 +113,7 @@ __device__ __forceinline__ void seg_prepare_one(const double* xrow, int64_t row,
   const double msq = np_sum<double>(fs, m) / (double)m;             // np.mean(q ** 2)
   double* z = Z + row * si.Lp + si.poff[s];
   double* st = stats + (row * si.nseg + s) * 4;
-  if (row_f32 ? row_f32[row] != 0 : all_f32 != 0) {
+  if (is32) {
     // _methods._var on float32: f32 pairwise sum, divide, x - mean, x * x, f32 pairwise sum, divide,
     // sqrt (np.mean = f32(f64(sum) / m) = the f32 division: the double rounding is innocuous)
     auto gx = [=](int k) -> float { return (float)x[k]; };
@@ -146,6 +146,13 @@ __device__ __forceinline__ void seg_prepare_one(const double* xrow, int64_t row,
   st[1] = sd;
   st[2] = msq;
   st[3] = 0.0;
+}
+
+// the row's float32 flag from the per-row flags (when given) or the batch's
+__device__ __forceinline__ void seg_prepare_one(const double* xrow, int64_t row, int s, const SegInfo& si,
+                                                int all_f32, const uint8_t* __restrict__ row_f32,
+                                                double* __restrict__ Z, double* __restrict__ stats) {
+  seg_prepare_one(xrow, row, s, si, row_f32 ? row_f32[row] != 0 : all_f32 != 0, Z, stats);
 }
 
 __global__ __launch_bounds__(256) void k_seg_prepare(const double* __restrict__ idx, int64_t N, SegInfo si,
@@ -2146,12 +2153,15 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(NB == 
 
 // rows of the split copies with a zero-variance / f32-unsafe flag (S32 flag word bits 1, 2): compacted
 // into list[*count] (order irrelevant: the pools are selected by (score, row))
+__device__ __forceinline__ void flag_row(const float* S32, int64_t r, int* list, int* count) {
+  const int f = __float_as_int(S32[(r >> 2) * 16 + 12 + (r & 3)]);
+  if (f & 3) list[atomicAdd(count, 1)] = (int)r;
+}
+
 __global__ __launch_bounds__(256) void k_flag_rows(const float* __restrict__ S32, int64_t N, int* __restrict__ list,
                                                    int* __restrict__ count) {
-  for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < N; r += (int64_t)gridDim.x * blockDim.x) {
-    const int f = __float_as_int(S32[(r >> 2) * 16 + 12 + (r & 3)]);
-    if (f & 3) list[atomicAdd(count, 1)] = (int)r;
-  }
+  for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < N; r += (int64_t)gridDim.x * blockDim.x)
+    flag_row(S32, r, list, count);
 }
 
 // one flagged row against one scanned query: the f64 statistics as k_scan0f's insert
@@ -5636,8 +5646,7 @@ __global__ __launch_bounds__(64) void k_seg_prepare_pack0(const double* __restri
 // accumulator r_j) and its normalised values written by the group's lanes (m / 8 divisions each), then the
 // split level-0 copy as k_seg_prepare_pack0.  The serial form has one lane walk each segment three times and
 // divide every value.  Same operations as seg_prepare_one, so bit-identical.
-__device__ __forceinline__ void seg_prepare_coop(const double* xrow, int64_t row, int s, const SegInfo& si,
-                                                 int all_f32, const uint8_t* __restrict__ row_f32,
+__device__ __forceinline__ void seg_prepare_coop(const double* xrow, int64_t row, int s, const SegInfo& si, bool is32,
                                                  double* __restrict__ Z, double* __restrict__ stats, int j) {
   const double* x = xrow + si.src[s];
   const int m = si.len[s], plen = si.plen[s];
@@ -5647,7 +5656,7 @@ __device__ __forceinline__ void seg_prepare_coop(const double* xrow, int64_t row
   const double msq = coop_sum<double>([=](int k) -> double { return x[k] * x[k]; }, m, j) / (double)m;      // mean(q**2)
   double* z = Z + row * si.Lp + si.poff[s];
   double* st = stats + (row * si.nseg + s) * 4;
-  if (row_f32 ? row_f32[row] != 0 : all_f32 != 0) {
+  if (is32) {
     const float mean32 = coop_sum<float>([=](int k) -> float { return (float)x[k]; }, m, j) / (float)m;
     const float sd32 = sqrtf(coop_sum<float>([=](int k) -> float { const float d = (float)x[k] - mean32; return d * d; },
                                              m, j) / (float)m);
@@ -5669,6 +5678,12 @@ __device__ __forceinline__ void seg_prepare_coop(const double* xrow, int64_t row
     st[2] = msq;
     st[3] = 0.0;
   }
+}
+
+__device__ __forceinline__ void seg_prepare_coop(const double* xrow, int64_t row, int s, const SegInfo& si,
+                                                 int all_f32, const uint8_t* __restrict__ row_f32,
+                                                 double* __restrict__ Z, double* __restrict__ stats, int j) {
+  seg_prepare_coop(xrow, row, s, si, row_f32 ? row_f32[row] != 0 : all_f32 != 0, Z, stats, j);
 }
 
 __global__ __launch_bounds__(64) void k_seg_prepare_pack0_coop(const double* __restrict__ idx, int64_t N, SegInfo si,
@@ -5967,15 +5982,12 @@ __host__ __device__ __forceinline__ int64_t ov_frag(int64_t row, int kb, int nkb
   return ((row >> 4) * nkb + kb) * kZ16Tile + ((g << 4) + (row & 15)) * 8;
 }
 
-__global__ void k_packov(const double* __restrict__ Z, const double* __restrict__ S, int64_t N, int Lp, OvLayout o,
-                         _Float16* __restrict__ Zo, float* __restrict__ So) {
-  const int64_t rows = z16_rows(N);
-  const int per = o.nkb * 32;
-  const int GS = ov_gsize(o.ng, o.nc);
-  const int64_t total = rows * per;
-  for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t r = t / per;
-    const int c = (int)(t % per), kb = c >> 5, k = c & 31;
+// one (row, value) of the split overall copies (row r < z16_rows(N), value c < 32 nkb)
+__device__ __forceinline__ void packov_elem(const double* __restrict__ Z, const double* __restrict__ S, int64_t N,
+                                            int Lp, const OvLayout& o, _Float16* __restrict__ Zo,
+                                            float* __restrict__ So, int64_t r, int c) {
+    const int GS = ov_gsize(o.ng, o.nc);
+    const int kb = c >> 5, k = c & 31;
     double z = 0.0;
     if (r < N)
       for (int i = 0; i < o.ng; ++i)
@@ -6015,6 +6027,55 @@ __global__ void k_packov(const double* __restrict__ Z, const double* __restrict_
       gp[4 * o.nc + rr] = __int_as_float(flag);
       gp[4 * o.nc + 4 + rr] = roff;
     }
+}
+
+__global__ void k_packov(const double* __restrict__ Z, const double* __restrict__ S, int64_t N, int Lp, OvLayout o,
+                         _Float16* __restrict__ Zo, float* __restrict__ So) {
+  const int64_t rows = z16_rows(N);
+  const int per = o.nkb * 32;
+  const int64_t total = rows * per;
+  for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x)
+    packov_elem(Z, S, N, Lp, o, Zo, So, t / per, (int)(t % per));
+}
+
+// Appending M rows to a resident corpus of N0 (hq_seg_append), one launch: one wave per new row N0 + i runs
+// k_seg_prepare_pack0's steps (the row's segments from an LDS copy, then its split level-0 copy), then the
+// row's split overall copy (packov_elem) and its entry of the flagged-row list (flag_row); the blocks past
+// N1 = N0 + M write the pad rows up to z16_rows(N1).  Every write lands in rows >= N0 (the layouts address by
+// row: z16_elem, ov_frag, the 4-row statistics groups), so resident rows sharing a tile or a group with N0
+// keep their bytes; the copies are those of the packing kernels run on the N1 rows.  COOP: the
+// lane-cooperative statistics (k_seg_prepare_pack0_coop's shapes).  Z16 / Zo / flags may be null.
+template <bool COOP>
+__global__ __launch_bounds__(64) void k_seg_append(const double* __restrict__ idx, int64_t M, int64_t N0, SegInfo si,
+                                                   int all_f32, const uint8_t* __restrict__ row_f32, double* Z,
+                                                   double* stats, _Float16* Z16, float* S32, OvLayout o,
+                                                   _Float16* Zo, float* So, int* flags) {
+  extern __shared__ double xs[];  // L values
+  const int lane = threadIdx.x;
+  const int64_t N1 = N0 + M, rows = z16_rows(N1);
+  const int per = o.nkb * 32;
+  for (int64_t row = N0 + blockIdx.x; row < rows; row += gridDim.x) {
+    if (row < N1) {
+      const int64_t i = row - N0;
+      const double* src = idx + i * si.L;
+      HQ_GUARD(src, idx, M * si.L - (si.L - 1));
+      const bool is32 = row_f32 ? row_f32[i] != 0 : all_f32 != 0;
+      for (int k = lane; k < si.L; k += 64) xs[k] = src[k];
+      __syncthreads();
+      if (COOP) {
+        for (int sg = lane >> 3; sg < si.nseg; sg += 8) seg_prepare_coop(xs, row, sg, si, is32, Z, stats, lane & 7);
+      } else {
+        for (int sg = lane; sg < si.nseg; sg += 64) seg_prepare_one(xs, row, sg, si, is32, Z, stats);
+      }
+      __threadfence_block();
+      __syncthreads();
+    }
+    if (Z16 && lane < 32) pack0_elem(Z, stats, N1, si.Lp, si.plen[0], si.nseg, Z16, S32, row, lane);
+    if (Zo)
+      for (int c = lane; c < per; c += 64) packov_elem(Z, stats, N1, si.Lp, o, Zo, So, row, c);
+    // lane 0 wrote the row's flag word (pack0_elem, value 0) just above
+    if (flags && lane == 0 && row < N1) flag_row(S32, row, flags + 1, flags);
+    __syncthreads();
   }
 }
 
@@ -7483,6 +7544,39 @@ int hq_seg_packov_split(const double* Z, const double* S, int64_t N, int L, void
   if (blocks > 16384) blocks = 16384;
   hipLaunchKernelGGL(k_packov, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, Z, S, N, si.Lp, o,
                      reinterpret_cast<_Float16*>(Zo16), So32);
+  HQ_CHECK_LAUNCH();
+  return HQ_OK;
+}
+
+int hq_seg_append(const double* idx, int64_t M, int L, int src_f32, const uint8_t* row_f32, int64_t N0, double* Z,
+                  double* stats, void* Z16, float* S32, void* Zov16, float* Sov32, int* flags, hq_stream_t stream) {
+  if (L <= 0 || M < 0 || N0 < 0) return fail(HQ_E_INVALID, "bad shape N0=%lld M=%lld L=%d", (long long)N0, (long long)M, L);
+  if (L > 4096) return fail(HQ_E_UNSUPPORTED, "L=%d (<= 4096)", L);
+  if (M == 0) return HQ_OK;
+  if (!idx || !Z || !stats) return fail(HQ_E_INVALID, "null buffer");
+  if ((Z16 == nullptr) != (S32 == nullptr) || (Zov16 == nullptr) != (Sov32 == nullptr))
+    return fail(HQ_E_INVALID, "a split copy needs both of its buffers");
+  if (flags && !S32) return fail(HQ_E_INVALID, "the flagged-row list needs the level-0 copies");
+  if (N0 + M >= 0x7FFFFFFF) return fail(HQ_E_UNSUPPORTED, "N=%lld rows (int32 row ids)", (long long)(N0 + M));
+  SegInfo si;
+  seg_info(L, si);
+  if (si.nseg == 0) return fail(HQ_E_INVALID, "no level structure for L=%d", L);
+  if (Z16 && si.plen[0] > 32) return fail(HQ_E_INVALID, "level-0 copies with a level-0 segment of %d values", si.plen[0]);
+  OvLayout o = {};
+  if (Zov16 && !ov_layout(L, o)) return fail(HQ_E_INVALID, "overall copies without a split overall layout (L=%d)", L);
+  hipStream_t s = (hipStream_t)stream;
+  if (flags && N0 == 0) HQ_CHECK_HIP(hipMemsetAsync(flags, 0, sizeof(int), s));  // an empty corpus lists no rows
+  const int64_t blocks = z16_rows(N0 + M) - N0;  // the new rows, then the pad rows
+  const dim3 grid((unsigned)(blocks < 65536 ? blocks : 65536));
+  if (seg_small(si) && si.nseg <= 8 && opt(OPT_PREP_COOP, 1) != 0) {
+    hipLaunchKernelGGL(k_seg_append<true>, grid, dim3(64), (size_t)8 * si.L, s, idx, M, N0, si, src_f32 ? 1 : 0, row_f32,
+                       Z, stats, reinterpret_cast<_Float16*>(Z16), S32, o, reinterpret_cast<_Float16*>(Zov16), Sov32,
+                       flags);
+  } else {
+    hipLaunchKernelGGL(k_seg_append<false>, grid, dim3(64), (size_t)8 * si.L, s, idx, M, N0, si, src_f32 ? 1 : 0, row_f32,
+                       Z, stats, reinterpret_cast<_Float16*>(Z16), S32, o, reinterpret_cast<_Float16*>(Zov16), Sov32,
+                       flags);
+  }
   HQ_CHECK_LAUNCH();
   return HQ_OK;
 }

@@ -178,6 +178,32 @@ class HilbertQuantizer:
         return {"total_models": len(self._model_registry),
                 "model_ids": [m.metadata.model_name for m in self._model_registry]}
 
+    @staticmethod
+    def _validate_quantized_model(model):
+        if not isinstance(model, QuantizedModel):
+            raise ValidationError("Invalid quantized model type")
+        if model.compressed_data is None or len(model.compressed_data) == 0:
+            raise ValidationError("Quantized model has no compressed data")
+        if model.parameter_count <= 0:
+            raise ValidationError("Invalid parameter count in quantized model")
+
+    def add_model_to_registry(self, quantized_model: QuantizedModel) -> None:
+        """api.py:299-308.  The next registry search appends the model's index to the resident corpus
+        (ProgressiveSimilaritySearchEngine._pool_acquire) instead of rebuilding it."""
+        self._validate_quantized_model(quantized_model)
+        self._model_registry.append(quantized_model)
+        self.logger.info(f"Added model {quantized_model.metadata.model_name} to registry")
+
+    def remove_model_from_registry(self, model_id: str) -> bool:
+        """api.py:310-325: drop the first model of that name; False when there is none.  A model removed before
+        the registry's end breaks the resident corpus's prefix, so the next registry search rebuilds it."""
+        for i, model in enumerate(self._model_registry):
+            if model.metadata.model_name == model_id:
+                del self._model_registry[i]
+                self.logger.info(f"Removed model {model_id} from registry")
+                return True
+        return False
+
     def clear_registry(self):
         self._model_registry.clear()
 

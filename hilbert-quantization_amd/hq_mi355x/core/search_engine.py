@@ -124,7 +124,7 @@ class PendingSearch:
     synchronous paths (small corpora, dense exact path)."""
 
     __slots__ = ("done", "qp", "out", "res", "cnt", "forced", "nredo", "event", "threshold", "M", "K_out", "kp",
-                 "ring")
+                 "ring", "counted")
 
     def __init__(self, done=None, qp=None, out=None, res=None, cnt=None, forced=None, nredo=None, event=None,
                  threshold=0.0, M=0, K_out=0, kp=0, ring=None):
@@ -132,6 +132,7 @@ class PendingSearch:
         self.nredo, self.event, self.threshold, self.M, self.K_out = nredo, event, threshold, M, K_out
         self.kp = kp  # the first pass's list length (the retry's base)
         self.ring = ring  # side reads: (ring entry, slot) of the batch's device counter
+        self.counted = False  # in the corpus's count of unfinished batches (IndexCorpus.append's writer rule)
 
 
 class IndexCorpus:
@@ -147,7 +148,14 @@ class IndexCorpus:
     Re-entrant: the reference calls its engines from ThreadPoolExecutor workers (core/video_search.py:806,
     854; core/streaming_processor.py:294), so one corpus may serve many threads at once.  Every piece of
     per-call device state (scan / re-rank workspace, redo counters) is keyed by thread as well as stream,
-    and the host-side caches (pinned buffers, statistics, adaptive list lengths) are guarded by a lock."""
+    and the host-side caches (pinned buffers, statistics, adaptive list lengths) are guarded by a lock.
+
+    Appendable: `append` writes new rows behind the resident ones (one hq_seg_append launch; nothing resident
+    moves, the buffers grow geometrically) and `reserve` sizes the buffers ahead of time.  Both are WRITERS:
+    searches are readers that take the rows past N for pad rows, so the caller must not append or reserve
+    while another thread is searching the same corpus, nor while a search queued on another stream may still
+    be running.  Submitted batches not yet finished are counted, and a writer called with that count non-zero
+    raises RuntimeError.  A search issued after `append` returns sees the new rows, on any stream."""
 
     # bound on |approximate - exact| score: the level-0 scan contracts in split f16 on the matrix cores
     # (|dscore| <= ~5.5e-6, hq_mi355x.h), the other scans in f64 (< 1e-13)
@@ -168,10 +176,67 @@ class IndexCorpus:
         self.dense_only = bool(self.prep.unsafe_rows().any()) if self.prep.f32 and self.N else False
         # the prepared layouts are written on the building thread's stream: a search on another stream waits
         # for them (an event wait queued on the device, no host sync)
+        self._pending = 0  # submitted progressive batches not yet finished (the writer rule)
+        self._mark_ready()
+        self._warm_redo(x)
+
+    def _mark_ready(self):
         self._built_on = K.stream()
         self._ready = torch().cuda.Event()
         self._ready.record()
-        self._warm_redo(x)
+
+    def _writer(self, what: str):
+        """Entry of a writer (append / reserve): no submitted batch unfinished; ordered after the last writer."""
+        with _lock(self):
+            if self._pending:
+                raise RuntimeError(f"IndexCorpus.{what} with {self._pending} submitted search batch(es) unfinished: "
+                                   "call progressive_finish first")
+        if K.stream() != self._built_on:
+            torch().cuda.current_stream().wait_event(self._ready)
+
+    def reserve(self, capacity: int) -> int:
+        """Room for `capacity` rows without another reallocation (device-to-device copies of the resident
+        layouts when the buffers grow).  A writer, as `append`.  Returns the capacity."""
+        self._writer("reserve")
+        if self.L <= 4096:  # longer index vectors are rebuilt by append: nothing to reserve
+            self.prep = K.seg_reserve(self.prep, int(capacity))
+            self._mark_ready()
+        return self.prep.cap
+
+    def append(self, indices, row_f32=None) -> int:
+        """Add the rows `indices` [M, L] (or [L]) behind the resident ones; appended row i gets the global id
+        id_base + N + i.  float32 input, or row_f32 flags, as in the constructor.  Runs on the calling thread's
+        stream; searches on other streams wait for it on the device.  Statistics and adaptive list lengths
+        are kept.  A writer: see the class docstring.  Returns the new N."""
+        t = torch()
+        f32 = _is_f32(indices)
+        x = _f64(indices)
+        if x.dim() == 1:
+            x = x.view(1, -1)
+        if x.dim() != 2 or int(x.shape[1]) != self.L:
+            raise ValueError(f"IndexCorpus.append expects [M, {self.L}] index vectors")
+        M, N0 = int(x.shape[0]), self.N
+        flags = None if f32 or row_f32 is None else np.asarray(row_f32, dtype=bool).reshape(-1)
+        if flags is not None and flags.size != M:
+            raise ValueError("row_f32 needs one flag per row")
+        self._writer("append")
+        if M == 0:
+            return self.N
+        if self.L > 4096:
+            # hq_seg_append takes L <= 4096: rebuild from the concatenated raw rows (aux bit 1: float32 source)
+            old32 = to_np((self.prep.S[:, 0, 3].to(t.int64) & 1).bool()) if self.prep.f32 else np.zeros(N0, dtype=bool)
+            new32 = np.full(M, f32, dtype=bool) if flags is None else flags
+            all_flags = np.concatenate([old32, new32])
+            prep = K.seg_prepare(t.cat([self.prep.R, x]), row_f32=all_flags if all_flags.any() else None)
+            prep = K.flag_rows(K.packov(K.pack0(prep)))
+        else:
+            prep = K.seg_append(self.prep, x, src_f32=f32, row_f32=flags)
+        # the new rows' float32 values outside the scans' model (one host sync, float32 rows only)
+        if (f32 or (flags is not None and flags.any())) and not self.dense_only:
+            self.dense_only = bool((prep.S[N0:, :, 3] >= 2.0).any())
+        self.prep, self.N = prep, prep.N
+        self._mark_ready()
+        return self.N
 
     def _warm_redo(self, x):
         """Once per process, with the first corpus built: one 1-query progressive batch whose list is marked
@@ -490,21 +555,40 @@ class IndexCorpus:
                               event=ev, threshold=float(threshold), M=M, K_out=K_out, kp=kp, ring=ring)
             with _lock(self):
                 ring[0][2][ring[1]] = p
-            return p
+            return self._count(p)
         # the counter's value leaves now, behind the re-rank (a last-workgroup write of it to the pinned int from
         # the re-rank kernel measured slower: 21 -> 43 us, every workgroup's release fence)
         host = self._pinned(nredo.dtype)
         host.copy_(nredo, non_blocking=True)
         ev = t.cuda.Event()
         ev.record()
-        return PendingSearch(qp=qp, out=(oid, odet, ocnt), res=res, cnt=cnt, forced=forced,
-                             nredo=host, event=ev, threshold=float(threshold), M=M, K_out=K_out, kp=kp)
+        return self._count(PendingSearch(qp=qp, out=(oid, odet, ocnt), res=res, cnt=cnt, forced=forced,
+                                         nredo=host, event=ev, threshold=float(threshold), M=M, K_out=K_out, kp=kp))
+
+    def _count(self, p: "PendingSearch") -> "PendingSearch":
+        """A batch left unfinished by progressive_submit: counted until progressive_finish (the writer rule)."""
+        with _lock(self):
+            self._pending += 1
+            p.counted = True
+        return p
+
+    def _uncount(self, p: "PendingSearch"):
+        with _lock(self):
+            if p.counted:
+                p.counted = False
+                self._pending -= 1
 
     def progressive_finish(self, p: "PendingSearch"):
         """Wait for a submitted batch's redo count (the one host sync) and recompute the queries whose
         list is not proven complete or where nothing passed, by the dense exact path."""
         if p.done is not None:
             return p.done
+        try:
+            return self._finish(p)
+        finally:
+            self._uncount(p)
+
+    def _finish(self, p: "PendingSearch"):
         t = torch()
         oid, odet, ocnt = p.out
         if p.ring is not None:
@@ -720,7 +804,15 @@ class ProgressiveSimilaritySearchEngine(*_bases("interfaces", "SimilaritySearchE
     def __init__(self, similarity_threshold: float = 0.1, max_candidates_per_level: int = 100):
         self.similarity_threshold = similarity_threshold
         self.max_candidates_per_level = max_candidates_per_level
-        self._pool_cache = None  # (index arrays of the last uniform pool, their resident IndexCorpus)
+        # [index arrays of the last uniform pool, their resident IndexCorpus, searches using it right now]
+        self._pool_cache = None
+        self._pool_stats = {"builds": 0, "appends": 0}
+
+    @property
+    def pool_stats(self) -> Dict[str, int]:
+        """How the resident pool corpus came about so far: full builds, and appends of a pool's new tail."""
+        with _lock(self):
+            return dict(self._pool_stats)
 
     # ---- structure -----------------------------------------------------------------------------
     def _parse_index_structure(self, indices, total_space: int) -> List[LevelConfig]:
@@ -736,19 +828,48 @@ class ProgressiveSimilaritySearchEngine(*_bases("interfaces", "SimilaritySearchE
         return IndexCorpus(C, row_f32=flags)
 
     def _pool_corpus(self, pool) -> IndexCorpus:
+        """The resident corpus of a candidate pool (see _pool_acquire), for callers that only look at it."""
+        corpus = self._pool_acquire(pool)
+        self._pool_release(corpus)
+        return corpus
+
+    def _pool_acquire(self, pool) -> IndexCorpus:
         """The resident corpus of a candidate pool, re-used while the pool holds the same index arrays
         in the same order (the reference re-scores every candidate per call; re-uploading and
         re-preparing the pool per query was O(pool) host and PCIe work).  The arrays are kept
         referenced, so an identity match is a match; a QuantizedModel's hierarchical_indices are never
-        written after creation (the reference's pipeline builds a new array per model)."""
+        written after creation (the reference's pipeline builds a new array per model).
+
+        A pool that continues the cached one (the same arrays, then more: a registry that grew) appends its
+        tail to the resident corpus (IndexCorpus.append) instead of rebuilding it — unless another search is
+        using that corpus right now (append is a writer): then a fresh corpus is built, as for any other
+        pool.  Every acquire is paired with a _pool_release once the caller's search has finished."""
         arrays = [c.hierarchical_indices for c in pool]
         with _lock(self):  # threads searching one pool share one resident corpus (built once)
             hit = self._pool_cache
-            if hit is not None and len(hit[0]) == len(arrays) and all(a is b for a, b in zip(hit[0], arrays)):
-                return hit[1]
+            n = len(hit[0]) if hit is not None else 0
+            if hit is not None and n <= len(arrays) and all(a is b for a, b in zip(hit[0], arrays)):
+                if n == len(arrays):
+                    hit[2] += 1
+                    return hit[1]
+                if hit[2] == 0 and hit[1]._pending == 0:
+                    tail = arrays[n:]
+                    flags = np.array([_is_f32(r) for r in tail], dtype=bool)
+                    hit[1].append(np.stack([np.asarray(r, dtype=np.float64) for r in tail]), row_f32=flags)
+                    hit[0].extend(tail)
+                    hit[2] += 1
+                    self._pool_stats["appends"] += 1
+                    return hit[1]
             corpus = self._corpus(arrays)
-            self._pool_cache = (arrays, corpus)
+            self._pool_cache = [arrays, corpus, 1]
+            self._pool_stats["builds"] += 1
             return corpus
+
+    def _pool_release(self, corpus: IndexCorpus):
+        with _lock(self):
+            hit = self._pool_cache
+            if hit is not None and hit[1] is corpus:
+                hit[2] -= 1
 
     def _scores_at_level(self, q: np.ndarray, cands: Sequence[np.ndarray], level: int) -> np.ndarray:
         """compare_indices_at_level(q, c, level) for every candidate, on the GPU."""
@@ -841,9 +962,13 @@ class ProgressiveSimilaritySearchEngine(*_bases("interfaces", "SimilaritySearchE
             return []
         q = _idx(query_indices)
         if self._uniform(q, candidate_pool):
-            corpus = self._pool_corpus(candidate_pool)
-            ids, ov, lv = corpus.brute_force(q[None], min(max_results, len(candidate_pool)))
-            return self._results(candidate_pool, to_np(ids)[0], to_np(ov)[0], to_np(lv)[0], with_error=False)
+            corpus = self._pool_acquire(candidate_pool)
+            try:
+                ids, ov, lv = corpus.brute_force(q[None], min(max_results, len(candidate_pool)))
+                ids, ov, lv = to_np(ids), to_np(ov), to_np(lv)  # the search has finished: copies wait for it
+            finally:
+                self._pool_release(corpus)
+            return self._results(candidate_pool, ids[0], ov[0], lv[0], with_error=False)
         ov, lv = self._overall_many(q, [c.hierarchical_indices for c in candidate_pool])
         order = np.argsort(-ov, kind="stable")[:max_results]
         return self._results(candidate_pool, order, ov[order], lv[order], with_error=False)
@@ -856,10 +981,14 @@ class ProgressiveSimilaritySearchEngine(*_bases("interfaces", "SimilaritySearchE
         if not self._parse_index_structure(q, len(q)):
             return []
         if self._uniform(q, candidate_pool):
-            corpus = self._pool_corpus(candidate_pool)
-            ids, ov, lv, cnt = corpus.progressive(q[None], max_results, self.similarity_threshold,
-                                                  self.max_candidates_per_level)
-            return self._results(candidate_pool, to_np(ids)[0], to_np(ov)[0], to_np(lv)[0], int(to_np(cnt)[0]))
+            corpus = self._pool_acquire(candidate_pool)
+            try:
+                ids, ov, lv, cnt = corpus.progressive(q[None], max_results, self.similarity_threshold,
+                                                      self.max_candidates_per_level)
+                ids, ov, lv, cnt = to_np(ids), to_np(ov), to_np(lv), to_np(cnt)
+            finally:
+                self._pool_release(corpus)
+            return self._results(candidate_pool, ids[0], ov[0], lv[0], int(cnt[0]))
         return self._progressive_mixed(q, candidate_pool, max_results)
 
     def progressive_search_batch(self, queries: Sequence, candidate_pool: List[QuantizedModel],
@@ -873,12 +1002,15 @@ class ProgressiveSimilaritySearchEngine(*_bases("interfaces", "SimilaritySearchE
         if not qs or any(len(q) != L for q in qs) or L == 0 or not self._parse_index_structure(qs[0], L) \
                 or not self._uniform(qs[0], candidate_pool):
             return [self.progressive_search(q, candidate_pool, max_results) for q in qs]
-        corpus = self._pool_corpus(candidate_pool)
-        Qa, qflags = _stack_rows(qs)
-        ids, ov, lv, cnt = corpus.progressive(Qa if qflags is None else (Qa, qflags), max_results,
-                                              self.similarity_threshold,
-                                              self.max_candidates_per_level)
-        ids, ov, lv, cnt = to_np(ids), to_np(ov), to_np(lv), to_np(cnt)
+        corpus = self._pool_acquire(candidate_pool)
+        try:
+            Qa, qflags = _stack_rows(qs)
+            ids, ov, lv, cnt = corpus.progressive(Qa if qflags is None else (Qa, qflags), max_results,
+                                                  self.similarity_threshold,
+                                                  self.max_candidates_per_level)
+            ids, ov, lv, cnt = to_np(ids), to_np(ov), to_np(lv), to_np(cnt)
+        finally:
+            self._pool_release(corpus)
         return [self._results(candidate_pool, ids[i], ov[i], lv[i], int(cnt[i])) for i in range(len(qs))]
 
     def _progressive_mixed(self, q, pool, max_results):

@@ -240,9 +240,14 @@ def seg_padded_len(L: int) -> int:
 class Prepared:
     """Device-resident prepared index vectors: raw R [N, L] f64, Z [N, Lp] f64 (segment padded,
     normalised) and stats S [N, nseg, 4] (mean, std, mean of squares, aux).  Built once per corpus.
-    f32: some rows are float32 index vectors (aux bit 1; hq_seg_prepare_src / _rows)."""
+    f32: some rows are float32 index vectors (aux bit 1; hq_seg_prepare_src / _rows).
 
-    __slots__ = ("R", "Z", "S", "L", "N", "nseg", "Lp", "Z16", "S32", "F0", "Zov16", "Sov32", "f32", "all32")
+    cap: the rows the buffers behind R / Z / S hold (seg_reserve / seg_append); R, Z, S are then the
+    length-N prefix views of `base` = (R, Z, S) capacity buffers, and Z16 / S32 / Zov16 / Sov32 / F0 are
+    sized for cap rows (their valid extents are those of N rows).  cap == N, base None: built to size."""
+
+    __slots__ = ("R", "Z", "S", "L", "N", "nseg", "Lp", "Z16", "S32", "F0", "Zov16", "Sov32", "f32", "all32", "cap",
+                 "base")
 
     def __init__(self, R, Z, S, L, f32: bool = False, all32: bool = False):
         self.R, self.Z, self.S, self.L = R, Z, S, int(L)
@@ -254,6 +259,7 @@ class Prepared:
         self.Z16 = self.S32 = None  # split-f16 level-0 copies for the level-0 scan (pack0)
         self.F0 = None  # a corpus's flagged rows of the level-0 copies, listed once (flag_rows)
         self.Zov16 = self.Sov32 = None  # split-f16 copies of every level for the overall scan (packov)
+        self.cap, self.base = self.N, None
 
     def rows(self, sel):
         """Sub-set of rows (device index tensor) as a new Prepared (level-0 copies re-packed on demand)."""
@@ -365,6 +371,82 @@ def flag_rows(p: Prepared, exc=None) -> Prepared:
     p.F0 = t.empty(1 + p.N, dtype=t.int32, device=p.Z.device)
     _chk(_L().hq_seg_flag_rows(ptr(p.S32), p.N, ptr(p.F0), stream()), exc)
     return p
+
+
+def _rows16(n: int) -> int:
+    return (n + 15) // 16 * 16 + PAD0
+
+
+def _rows4(n: int) -> int:
+    return (n + 3) // 4 * 4 + PAD0
+
+
+def seg_reserve(p: Prepared, capacity: int) -> Prepared:
+    """A Prepared of the same N rows whose buffers hold `capacity` rows (p itself when they already do):
+    new buffers, device-to-device copies of the valid extents of every layout p carries.  The rows past N
+    are written by seg_append."""
+    cap = int(capacity)
+    if cap <= p.cap and p.base is not None:
+        return p
+    cap = max(cap, p.cap)
+    t = torch()
+    dev, N = p.Z.device, p.N
+    Rb = t.empty((cap, p.L), dtype=t.float64, device=dev)
+    Zb = t.empty((cap, p.Lp), dtype=t.float64, device=dev)
+    Sb = t.empty((cap, p.nseg, 4), dtype=t.float64, device=dev)
+    Rb[:N].copy_(p.R)
+    Zb[:N].copy_(p.Z)
+    Sb[:N].copy_(p.S)
+    q = Prepared(Rb[:N], Zb[:N], Sb[:N], p.L, p.f32, p.all32)
+    q.cap, q.base = cap, (Rb, Zb, Sb)
+    if p.Z16 is not None:
+        q.Z16 = t.empty((_rows16(cap), 64), dtype=t.float16, device=dev)
+        q.S32 = t.empty((_rows4(cap), 4), dtype=t.float32, device=dev)
+        q.Z16[:_rows16(N)].copy_(p.Z16[:_rows16(N)])
+        q.S32[:_rows4(N)].copy_(p.S32[:_rows4(N)])
+    if p.Zov16 is not None:
+        q.Zov16 = t.empty((_rows16(cap), p.Zov16.shape[1]), dtype=t.float16, device=dev)
+        q.Sov32 = t.empty((_rows4(cap) // 4, p.Sov32.shape[1]), dtype=t.float32, device=dev)
+        q.Zov16[:_rows16(N)].copy_(p.Zov16[:_rows16(N)])
+        q.Sov32[:_rows4(N) // 4].copy_(p.Sov32[:_rows4(N) // 4])
+    if p.F0 is not None:
+        q.F0 = t.empty(1 + cap, dtype=t.int32, device=dev)
+        q.F0[:1 + N].copy_(p.F0[:1 + N])  # the count and (at most N) listed rows
+    return q
+
+
+def seg_append(p: Prepared, rows, src_f32: bool = False, row_f32=None, exc=None) -> Prepared:
+    """p grown by `rows` [M, L] (src_f32 / row_f32 as seg_prepare): one hq_seg_append launch writes the new
+    rows' R / Z / S and every split layout p carries (pack0, packov, flag_rows) behind the resident rows, which
+    do not move.  Beyond the capacity the buffers grow geometrically (x 2, at least the need: seg_reserve).
+    Returns a new Prepared over the same buffers; p must not be scanned afterwards (what it took for pad rows
+    are real rows now), and scans of p still running on other streams must have finished before the call."""
+    t = torch()
+    r2 = _contig((rows if rows.dim() == 2 else rows.view(1, -1)).to(t.float64))
+    M, L = r2.shape
+    if L != p.L:
+        raise ValueError(f"appended index length {L} != corpus index length {p.L}")
+    rf = None
+    any32 = all32 = bool(src_f32)
+    if row_f32 is not None and not src_f32:
+        flags = np.asarray(row_f32, dtype=bool).reshape(-1)
+        if flags.size != M:
+            raise ValueError("row_f32 needs one flag per row")
+        any32, all32 = bool(flags.any()), bool(flags.all())
+        rf = _contig(t.from_numpy(flags.astype(np.uint8)).to(r2.device))
+    if M == 0:
+        return p
+    N0, N1 = p.N, p.N + M
+    if N1 > p.cap or p.base is None:
+        p = seg_reserve(p, max(N1, 2 * p.cap))
+    Rb, Zb, Sb = p.base
+    Rb[N0:N1].copy_(r2)
+    _chk(_L().hq_seg_append(ptr(r2), M, L, 1 if src_f32 else 0, ptr(rf), N0, ptr(Zb), ptr(Sb), ptr(p.Z16), ptr(p.S32),
+                            ptr(p.Zov16), ptr(p.Sov32), ptr(p.F0), stream()), exc)
+    q = Prepared(Rb[:N1], Zb[:N1], Sb[:N1], L, p.f32 or any32, all32 and (p.all32 or N0 == 0))
+    q.cap, q.base = p.cap, p.base
+    q.Z16, q.S32, q.Zov16, q.Sov32, q.F0 = p.Z16, p.S32, p.Zov16, p.Sov32, p.F0
+    return q
 
 
 def level_scores(q: Prepared, c: Prepared, level: int, exc=None):

@@ -285,6 +285,20 @@ int hq_scan0_topk_split_fl(const void* Zq16, const float* Sq32, const double* Sq
 int hq_seg_packov_info(int L, int* nkb, int* ng, int* nc, int* group_floats);
 int hq_seg_packov_split(const double* Z, const double* S, int64_t N, int L, void* Zo16, float* So32,
                         hq_stream_t stream);
+/* hq_seg_append: grow a resident corpus of N0 rows by the M rows of idx (f64 [M, L]; src_f32 / row_f32 [M] as
+ *   hq_seg_prepare_rows) in ONE launch, without moving a resident row.  Z, stats, Z16, S32, Zov16, Sov32 and
+ *   flags are the BASES of the corpus's buffers, each with room for N1 = N0 + M rows and its padding
+ *   (round_up(N1, 16) + 48 rows of Z16 / Zov16, round_up(N1, 4) + 48 rows of S32 / Sov32, 1 + N1 ints of flags).
+ *   One wave per new row writes its Z, stats, split level-0 copy, split overall copy and flag-list entry
+ *   (flags[0] grows by an atomic add; N0 = 0 clears it first); further workgroups write the pad rows after
+ *   N1.  Afterwards every buffer equals, byte for byte, what hq_seg_prepare_rows, hq_seg_pack0_split,
+ *   hq_seg_packov_split and hq_seg_flag_rows (as a set: the list has no order) write for the N1 rows; only rows
+ *   >= N0 are written, so rows below N0 in N0's 16-row tile or 4-row group keep their bytes.  Z16 / S32 may be
+ *   NULL (level-0 segment longer than 32 values), Zov16 / Sov32 too (no hq_seg_packov_info layout), flags too.
+ *   L <= 4096 (else HQ_E_UNSUPPORTED); M = 0 writes nothing.  The caller orders the call after every scan
+ *   that reads the corpus (stream order or an event): readers of N0 rows treat [N0, ...) as pad rows.        */
+int hq_seg_append(const double* idx, int64_t M, int L, int src_f32, const uint8_t* row_f32, int64_t N0, double* Z,
+                  double* stats, void* Z16, float* S32, void* Zov16, float* Sov32, int* flags, hq_stream_t stream);
 size_t hq_scanov_workspace_size(int Q, int64_t N, int k);
 int hq_scanov_topk_split(const void* Zq16, const float* Sq32, const double* Sq, const double* Zq, int Q,
                          const void* Zc16, const float* Sc32, const double* Sc, const double* Zc, int64_t N, int L,
