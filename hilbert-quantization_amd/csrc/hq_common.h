@@ -47,11 +47,11 @@ enum Opt {
   OPT_PRECOMP_NT, OPT_PRECOMP_TREE_LDS, OPT_PRECOMP_PAD, OPT_PRECOMP_SKIP, OPT_PRECOMP_GRID, OPT_PRECOMP_PF,
   OPT_PRECOMP_DIAG,
   OPT_COS_KERNEL,
-  OPT_SAMPLE_STRIDE, OPT_SAMPLE_WAVES, OPT_SAMPLE_KTH, OPT_SAMPLE_VARIANT,
-  OPT_SCAN_V1, OPT_SCAN_NOSAMPLE, OPT_SCAN_EXPT, OPT_SCAN_VARIANT, OPT_SCAN_WPB, OPT_SCAN_PF, OPT_SCAN_NB, OPT_OV_WAVES, OPT_OV_OCC,
-  OPT_REFINE_GLOBAL, OPT_REFINE_EXPT, OPT_SEG_PREPARE_FLAT, OPT_SELECT_2STAGE, OPT_LEVEL_SCORES_V1, OPT_SCAN_SPLIT3, OPT_SCAN_OCC, OPT_SCANOV_SPLIT3, OPT_SAMPLE_HI,
-  OPT_PRECOMP_WS, OPT_PRECOMP_LEAF_ROT, OPT_PRECOMP_ORDER, OPT_SCANOV_V1, OPT_OV_PF, OPT_PRECOMP_G2REG,
-  OPT_REFINE_COOP, OPT_PRECOMP_COMPACT, OPT_PREP_COOP, OPT_POOL_SORT_MEM, OPT_REFINE_SMALL, OPT_FINAL_ROUNDS,
+  OPT_SAMPLE_KTH,
+  OPT_SCAN_V1,
+  OPT_REFINE_GLOBAL, OPT_SELECT_2STAGE, OPT_LEVEL_SCORES_V1,
+  OPT_PRECOMP_WS, OPT_PRECOMP_LEAF_ROT, OPT_PRECOMP_ORDER, OPT_PRECOMP_G2REG,
+  OPT_REFINE_COOP, OPT_PRECOMP_COMPACT, OPT_PREP_COOP, OPT_POOL_SORT_MEM, OPT_REFINE_SMALL,
   OPT_RANK_CT, OPT_RANK_WIN, OPT_RANK_SORT_NT, OPT_RANK_SORT_SMALL,
   OPT_COUNT
 };

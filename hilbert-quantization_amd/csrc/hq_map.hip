@@ -37,11 +37,11 @@ static const char* const kOptNames[OPT_COUNT] = {
     "precomp_nt", "precomp_tree_lds", "precomp_pad", "precomp_skip", "precomp_grid", "precomp_pf",
     "precomp_diag",
     "cos_kernel",
-    "sample_stride", "sample_waves", "sample_kth", "sample_variant",
-    "scan_v1", "scan_nosample", "scan_expt", "scan_variant", "scan_wpb", "scan_pf", "scan_nb", "ov_waves", "ov_occ",
-    "refine_global", "refine_expt", "seg_prepare_flat", "select_2stage", "level_scores_v1", "scan_split3", "scan_occ", "scanov_split3", "sample_hi",
-    "precomp_ws", "precomp_leaf_rot", "precomp_order", "scanov_v1", "ov_pf", "precomp_g2reg",
-    "refine_coop", "precomp_compact", "prep_coop", "pool_sort_mem", "refine_small", "final_rounds",
+    "sample_kth",
+    "scan_v1",
+    "refine_global", "select_2stage", "level_scores_v1",
+    "precomp_ws", "precomp_leaf_rot", "precomp_order", "precomp_g2reg",
+    "refine_coop", "precomp_compact", "prep_coop", "pool_sort_mem", "refine_small",
     "rank_ct", "rank_win", "rank_sort_nt", "rank_sort_small"};
 static int64_t g_opt_val[OPT_COUNT];
 static bool g_opt_set[OPT_COUNT];

@@ -827,42 +827,31 @@ __global__ __launch_bounds__(256) void k_scan(ScanArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// level-0 scan, wave-independent (the progressive search's filtering stage; k_scan handles the
-// overall mode and the arg-max).  One wave = 64 queries (4 MFMA column blocks of 16) x one corpus
-// chunk, 16 candidates per step:
-//   D[cand][query] = sum_k Zc[cand][k] Zq[query][k] with v_mfma_f64_16x16x4f64, A = candidates,
-//   B = queries.  Lane group g = lane >> 4 feeds the contiguous k range [g*KS, g*KS + KS), so each
-//   lane loads its candidate fragment with KS/2 16-byte loads straight from HBM/L2 (no LDS staging,
-//   no barriers); the query fragments stay in registers for the whole chunk.
-// Lane (g, j) owns queries 16b + j (b < 4) and candidates g + 4r (r < 4) of the step.
+// level-0 scan (the progressive search's filtering stage; k_scan handles the overall mode and the
+// arg-max).  One wave = 64 queries (4 MFMA column blocks of 16) x one corpus chunk, 16 candidates per
+// step: D[cand][query] = sum_k Zc[cand][k] Zq[query][k], A = candidates, B = queries; the query
+// fragments stay in registers for the whole chunk, the candidate fragments come straight from HBM/L2.
+// Lane (g, j) owns queries 16b + j (b < 4) and candidates 4g + r (r < 4) of the step (the MFMA D layout).
 // Filter without division: with base = 0.35 + 0.35 G/m, num = 0.6 (qs cs G / m + qm cm) and
-// den = msq_q + msq_c, score >= th  <=>  th - base <= 0  or  num >= (th - base) den.
-// th(query) = max(threshold, own K-th best, best K-th of any other wave for that query); the last
-// is exchanged through a per-query atomicMax in global memory (scores >= 0 order like their bit
-// patterns), so after the first chunks almost nothing reaches the insert path.  Every pruned
-// candidate is below the K-th best of some complete list, so the merged top-K is unchanged.
+// den = msq_q + msq_c >= 0, score >= T  <=>  base >= T  or  base + num / den >= T, i.e. with
+//   E = base - T = fma(G, c1, 0.35 - T),  num = fma(G, qA cs, qB cm),  d = fma(E, den, num)
+//   pass <=> max(E, d) >= 0       (d is one fma, its sign exact)
+// and a passing pair's list score is the same expression with the division (f32, 1-ulp reciprocal).
+// T = thl - kMarginF; k0 = 0.35 - T is a per-query constant (QConst).
 // ------------------------------------------------------------------------------------------------
 constexpr int kQW = 64;  // queries per wave
 constexpr int kCS = 16;  // candidates per step
 
 struct Scan0Args {
-  const double* Zq; const double* Sq; int Q;
-  const double* Zc; const double* Sc; int64_t N;
-  const float* Zq32; const float* Zc32;  // f64 kernels: unused
-  const _Float16* Zq16; const _Float16* Zc16;  // split kernels: level-0 rows [hi 32 | lo 32] (+kPad0 rows)
-  const float* Sq32; const float* Sc32;  // split kernels: level-0 (std, mean, msq, flag bits) per row
-  int Lp, nseg, P0;
+  const double* Sq; int Q;   // f64 statistics: flagged pairs (k_pool_select)
+  const double* Sc; int64_t N;
+  const _Float16* Zq16; const _Float16* Zc16;  // level-0 rows, tiled split fragments (z16_frag; + kPad0 rows)
+  const float* Sc32;         // level-0 (std, mean, msq, flag bits) per row, SoA groups of 4 rows
+  int nseg;
   double inv_m, c1;  // 1/m, 0.35/m
-  int K;
-  double thr0;       // initial threshold (-inf: none)
-  const double* th0; // per-query lower bound of the K-th best approximate score (sample pass) or null
-  int64_t id_base;
   int64_t chunk_len; int nchunks; int nqb;
-  double* ws_score; int64_t* ws_id; unsigned long long* gtau;
-  float* pool_s; int* pool_i; int* pool_n; int pool_cap;  // k_scan0f: per-query candidate pools
-  const void* qconst; // k_scan0g: per-query QConst table (k_sample_kth / k_scan_qprep)
-  int expt;          // HQ_SCAN_EXPT=3: count insert-path entries, passing pairs and list merges
-  unsigned long long* dbg;  // expt 3: [entries, passing pairs, list inserts]
+  float* pool_s; int* pool_i; int* pool_n; int pool_cap;  // per-query candidate pools
+  const void* qconst; // per-query QConst table (k_sample_kth)
 };
 
 __device__ __forceinline__ double rl_f64(double v, int l) {
@@ -873,17 +862,7 @@ __device__ __forceinline__ double rl_f64(double v, int l) {
   return *reinterpret_cast<double*>(&r);
 }
 
-// lane i <- lane i-1 (lane 0 keeps its own value): DPP wave_shr:1
-__device__ __forceinline__ int shr1_i32(int v) { return __builtin_amdgcn_update_dpp(v, v, 0x138, 0xF, 0xF, false); }
-__device__ __forceinline__ double shr1_f64(double v) {
-  int2 p = *reinterpret_cast<int2*>(&v);
-  p.x = shr1_i32(p.x);
-  p.y = shr1_i32(p.y);
-  return *reinterpret_cast<double*>(&p);
-}
-
-// approximate level-0 score of a pair with both stds non-zero (the insert path and the sample pass
-// use this same expression, so their values agree bit for bit)
+// approximate level-0 score of a pair with both stds non-zero, from the f64 statistics (flagged rows)
 __device__ __forceinline__ double approx0(double G, double c1, double qA, double qB, double qQ, double cs, double cm,
                                           double cq) {
   const double base = fma(G, c1, 0.35);
@@ -896,395 +875,16 @@ __device__ __forceinline__ double approx0(double G, double c1, double qA, double
 }
 
 typedef float flt4 __attribute__((ext_vector_type(4)));
-typedef float flt2 __attribute__((ext_vector_type(2)));
-
-// Z operand type of the f64 contraction (v_mfma_f64_16x16x4f64, C/D row (lane>>4) + 4r).
-template <bool F32> struct ZOps;
-template <> struct ZOps<false> {
-  typedef double T;
-  typedef dbl4 Acc;
-  static __device__ __forceinline__ Acc mfma(T a, T b, Acc c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
-  static __device__ __forceinline__ int row(int g, int r) { return g + 4 * r; }
-  static __device__ __forceinline__ const T* zq(const Scan0Args& a, int64_t q) { return a.Zq + q * a.Lp; }
-  static __device__ __forceinline__ const T* zc(const Scan0Args& a, int64_t c) { return a.Zc + c * a.Lp; }
-};
-
-#ifdef HQ_DIAG
-// f64 sources only (hq_seg_prepare without float32 rows): the constant branch compares means in f64
-template <int KS>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_scan0(Scan0Args a) {
-  typedef ZOps<false> Z;
-  typedef typename Z::T ZT;
-  typedef typename Z::Acc AccT;
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  double* qc = reinterpret_cast<double*>(smem);      // kQW x 4: 0.6 qs / m, 0.6 qm, msq, mean
-  double* ls = qc + kQW * 4;                          // kQW x K approx scores
-  int* li = reinterpret_cast<int*>(ls + kQW * a.K);   // kQW x K corpus rows
-  const int lane = threadIdx.x, g = lane >> 4, j = lane & 15;
-  const int blk = blockIdx.x, xcd = blk & 7, slot = blk >> 3;
-  const int chunk = xcd + 8 * (slot / a.nqb);
-  const int qb = slot % a.nqb;
-  if (chunk >= a.nchunks) return;
-  const int64_t c_begin = (int64_t)chunk * a.chunk_len;
-  int64_t c_end = c_begin + a.chunk_len;
-  if (c_end > a.N) c_end = a.N;
-  const int q0 = qb * kQW;
-  const int K = a.K;
-
-  // query fragments (registers, whole chunk), constants (LDS), thresholds (registers)
-  ZT qf[4][KS];
-  double th[4];
-  int qz = 0;  // bit b: query 16b + j has zero std
-#pragma unroll
-  for (int b = 0; b < 4; ++b) {
-    const int q = q0 + 16 * b + j;
-    const bool v = q < a.Q;
-    const ZT* zr = Z::zq(a, v ? q : 0) + g * KS;
-#pragma unroll
-    for (int t = 0; t < KS; ++t) qf[b][t] = v ? zr[t] : (ZT)0;
-    const double* st = a.Sq + (int64_t)(v ? q : 0) * a.nseg * 4;
-    const double qm = st[0], qs = st[1], qq = st[2];
-    if (g == 0) {
-      double* c = qc + (16 * b + j) * 4;
-      c[0] = (0.6 * a.inv_m) * qs;
-      c[1] = 0.6 * qm;
-      c[2] = qq;
-      c[3] = qm;
-    }
-    double t0 = a.thr0;
-    if (v && a.th0 && a.th0[q] > t0) t0 = a.th0[q];
-    th[b] = v ? t0 : __builtin_huge_val();
-    if (v && qs == 0.0) qz |= 1 << b;
-  }
-  for (int i = lane; i < kQW * K; i += 64) {
-    ls[i] = -__builtin_huge_val();
-    li[i] = -1;
-  }
-  const bool myq = q0 + lane < a.Q;  // lane's query for the global-threshold exchange
-
-  // candidate fragment of a step: row cs + j, k range [g*KS, g*KS + KS)
-  typedef double dbl2v __attribute__((ext_vector_type(2)));
-  auto load_frag = [&](int64_t cs, ZT* dst) {
-    int64_t c = cs + j;
-    if (c >= c_end) c = c_end - 1;
-    const ZT* p = Z::zc(a, c) + g * KS;
-    constexpr int W = 16 / sizeof(ZT);  // elements per 16-byte load
-    if constexpr ((KS % W) == 0) {
-      typedef ZT vec __attribute__((ext_vector_type(16 / sizeof(ZT))));
-#pragma unroll
-      for (int t = 0; t < KS; t += W) {
-        const vec v = *reinterpret_cast<const vec*>(p + t);
-#pragma unroll
-        for (int e = 0; e < W; ++e) dst[t + e] = v[e];
-      }
-    } else {
-#pragma unroll
-      for (int t = 0; t < KS; ++t) dst[t] = p[t];
-    }
-  };
-  // candidate statistics of a step for the lane's rows Z::row(g, r): mean, std, msq
-  auto load_stats = [&](int64_t cs, double* dst) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      int64_t c = cs + Z::row(g, r);
-      if (c >= c_end) c = c_end - 1;
-      const double* st = a.Sc + c * a.nseg * 4;
-      const dbl2v v = *reinterpret_cast<const dbl2v*>(st);
-      dst[3 * r] = v.x;
-      dst[3 * r + 1] = v.y;
-      dst[3 * r + 2] = st[2];
-    }
-  };
-  // MFMAs of one half (two 16-query blocks) of a step
-  auto mfma_half = [&](const int h, const ZT* f, AccT* acc) {
-    acc[0] = AccT{0, 0, 0, 0};
-    acc[1] = AccT{0, 0, 0, 0};
-#pragma unroll
-    for (int t = 0; t < KS; ++t) {  // two interleaved chains
-      acc[0] = Z::mfma(f[t], qf[2 * h][t], acc[0]);
-      acc[1] = Z::mfma(f[t], qf[2 * h + 1][t], acc[1]);
-    }
-  };
-  // filter of one half of the step starting at row cs: branch-free, so the scheduler can interleave
-  // it with the other half's MFMAs.  Returns the lane's pass bits (bit 4u + r).
-  auto filter_half = [&](const int h, const AccT* acc, const int64_t cs, const double* cst,
-                         double* qa, double* qbv, double* qqv) -> int {
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const double* c = qc + (16 * (2 * h + u) + j) * 4;
-      const dbl2v v0 = *reinterpret_cast<const dbl2v*>(c);
-      qa[u] = v0.x;
-      qbv[u] = v0.y;
-      qqv[u] = c[2];
-    }
-    int bits = 0;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const bool inval = cs + Z::row(g, r) >= c_end;
-      const bool zc = cst[3 * r + 1] == 0.0;
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const int b = 2 * h + u;
-        const double G = (double)acc[u][r];
-        const double R = th[b] - fma(G, a.c1, 0.35);
-        const double num = fma(G, qa[u] * cst[3 * r + 1], qbv[u] * cst[3 * r]);
-        const double den = qqv[u] + cst[3 * r + 2];
-        // zero-variance pairs go to the insert path, which evaluates and tests them exactly;
-        // rows past the chunk end never pass
-        const bool spec = zc | (((qz >> b) & 1) != 0);
-        const bool p = ((R <= 0.0) | (num >= R * den) | spec) & !inval;
-        bits |= (int)p << (4 * u + r);
-      }
-    }
-    return bits;
-  };
-  // insert the passing pairs of one half (rare once the thresholds are up)
-  auto insert_half = [&](const int h, const AccT* acc, const int64_t cs, const double* cst, const double* qa,
-                         const double* qbv, const double* qqv, const int bits) {
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int b = 2 * h + u;
-        unsigned long long m = __ballot((bits >> (4 * u + r)) & 1);
-        if (m == 0ull) continue;
-        const double csd = cst[3 * r + 1], cm = cst[3 * r];
-        const bool zq = (qz >> b) & 1, zc = csd == 0.0;
-        const double s = (zq || zc) ? const0(zq, zc, qc[(16 * b + j) * 4 + 3], cm)
-                                    : approx0((double)acc[u][r], a.c1, qa[u], qbv[u], qqv[u], csd, cm, cst[3 * r + 2]);
-        while (m) {
-          const int l = __builtin_ctzll(m);
-          m &= m - 1;
-          const int c_off = Z::row(l >> 4, r);
-          const double sc = rl_f64(s, l);
-          if (!(sc >= rl_f64(th[b], l))) continue;
-          const int qi = 16 * b + (l & 15);
-          const int id = (int)(cs + c_off);
-          double es = lane < K ? ls[qi * K + lane] : -__builtin_huge_val();
-          int ei = lane < K ? li[qi * K + lane] : -1;
-          const bool bt = (ei >= 0) && (es > sc || (es == sc && ei < id));
-          const int p = __popcll(__ballot(bt));
-          if (p >= K) continue;
-          const double us = shr1_f64(es);
-          const int ui = shr1_i32(ei);
-          if (lane > p) { es = us; ei = ui; }
-          if (lane == p) { es = sc; ei = id; }
-          if (lane < K) {
-            ls[qi * K + lane] = es;
-            li[qi * K + lane] = ei;
-          }
-          if (__builtin_amdgcn_readlane(ei, K - 1) >= 0) {
-            const double tau = rl_f64(es, K - 1);
-            if (j == (l & 15)) th[b] = tau > th[b] ? tau : th[b];
-            if (lane == 0 && tau > 0.0)
-              atomicMax(a.gtau + q0 + qi, (unsigned long long)__double_as_longlong(tau));
-          }
-        }
-      }
-  };
-  // 16 MFMAs interleaved with the filter's VALU work
-  auto interleave = [&]() {
-#pragma unroll
-    for (int i = 0; i < 2 * KS; ++i) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);
-    }
-  };
-
-  // Software pipeline: the MFMAs of one half run while the VALU filters the other half
-  //   block A: MFMA(step i, half 1)   || filter(step i, half 0)
-  //   block B: MFMA(step i+1, half 0) || filter(step i, half 1)
-  ZT cf[KS];
-  double cst[12];
-  load_frag(c_begin, cf);
-  load_stats(c_begin, cst);
-  AccT acc0[2], acc1[2];
-  mfma_half(0, cf, acc0);
-  unsigned long long gt_bits = 0ull;
-  int step = 0;
-  for (int64_t cs = c_begin; cs < c_end; cs += kCS, ++step) {
-    ZT cfn[KS];
-    double cstn[12];
-    load_frag(cs + kCS, cfn);  // unconditional (rows clamp to the chunk): keeps the wait counts exact
-    load_stats(cs + kCS, cstn);
-    double qa[2], qbv[2], qqv[2];
-    mfma_half(1, cf, acc1);
-    const int bits0 = filter_half(0, acc0, cs, cst, qa, qbv, qqv);
-    interleave();
-    if (__ballot(bits0 != 0)) insert_half(0, acc0, cs, cst, qa, qbv, qqv, bits0);
-    mfma_half(0, cfn, acc0);  // next step's first half (a harmless repeat of the last row at the end)
-    const int bits1 = filter_half(1, acc1, cs, cst, qa, qbv, qqv);
-    interleave();
-    if (__ballot(bits1 != 0)) insert_half(1, acc1, cs, cst, qa, qbv, qqv, bits1);
-#pragma unroll
-    for (int t = 0; t < KS; ++t) cf[t] = cfn[t];
-#pragma unroll
-    for (int t = 0; t < 12; ++t) cst[t] = cstn[t];
-    // ---- global thresholds, every 4 steps (applied from the next step) ----
-    if ((step & 3) == 0) {
-      if (gt_bits != 0ull) {
-        const double gd = __longlong_as_double((long long)gt_bits);
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-          const double v = __shfl(gd, 16 * b + j, 64);
-          th[b] = v > th[b] ? v : th[b];
-        }
-      }
-      if (myq) gt_bits = __atomic_load_n(a.gtau + q0 + lane, __ATOMIC_RELAXED);
-    }
-  }
-
-  // ---- this chunk's lists ----
-  for (int i = lane; i < kQW * K; i += 64) {
-    const int ql = i / K, jj = i % K;
-    const int q = q0 + ql;
-    if (q >= a.Q) continue;
-    const int64_t o = ((int64_t)chunk * a.Q + q) * K + jj;
-    const int id = li[i];
-    a.ws_score[o] = id >= 0 ? ls[i] : -__builtin_huge_val();
-    a.ws_id[o] = id >= 0 ? (int64_t)id + a.id_base : -1;
-  }
-}
-#endif  // HQ_DIAG
-
-// ------------------------------------------------------------------------------------------------
-// sample pass for k_scan0: a strided subset of the corpus (row i*stride) is scored with the same
-// MFMA contraction and the same approximate-score expression; each query gets a 256-bin histogram of
-// its sample scores over [0, 1].  The highest bin edge e/256 with >= K sample scores at or above it
-// is a lower bound of the K-th best score over the whole corpus (the sample is a subset), which
-// k_scan0 uses as its starting threshold, so only ~stride*K candidates per query reach its lists.
-// ------------------------------------------------------------------------------------------------
-constexpr int kBins = 256;
 
 struct SampleArgs {
-  const double* Zq; const double* Sq; int Q;
-  const double* Zc; const double* Sc; int64_t N;
-  const float* Zq32; const float* Zc32;
+  int Q; int64_t N;
   const _Float16* Zq16; const _Float16* Zc16;
   const float* Sq32; const float* Sc32;
-  int Lp, nseg, P0;
   double inv_m, c1;
   int64_t stride, S;
   int64_t chunk_len; int nchunks; int nqb;
-  int K;
-  unsigned int* hist;  // Q x kBins
-  float* top;          // k_sample_topf: Q x 4 nchunks x kTopT
+  float* top;          // Q x 4 nchunks x kTopT
 };
-
-#ifdef HQ_DIAG
-constexpr int kHRow = kBins / 2 + 1;  // LDS words per query histogram (odd: conflict-free rows)
-
-// Flush the top of a wave's per-query histograms (lane = query): bins from the top down until K
-// scores are covered.  Dropping lower bins only lowers global counts, so the edge k_hist_tau finds
-// stays a valid lower bound; the global top-K scores are all counted, so it stays as tight.
-__device__ void flush_hist_top(const uint32_t* hs, int q0, int Q, int K, unsigned int* hist) {
-  const int lane = threadIdx.x;
-  const int q = q0 + lane;
-  if (q >= Q) return;
-  const uint32_t* hq = hs + lane * kHRow;
-  unsigned int cum = 0;
-  for (int w = kBins / 2 - 1; w >= 0 && cum < (unsigned)K; --w) {
-    const uint32_t v = hq[w];
-    if (v == 0u) continue;
-    const unsigned hi = v >> 16, lo = v & 0xFFFFu;  // bins 2w + 1, 2w
-    unsigned int* h = hist + (int64_t)q * kBins + 2 * w;
-    if (hi) { atomicAdd(h + 1, hi); cum += hi; }
-    if (cum < (unsigned)K && lo) { atomicAdd(h, lo); cum += lo; }
-  }
-}
-
-template <int KS>
-__global__ __launch_bounds__(64) void k_sample_hist(SampleArgs a) {
-  typedef ZOps<false> Z;
-  typedef typename Z::T ZT;
-  typedef typename Z::Acc AccT;
-  auto zrow = [&](const double* p64, const float*, int64_t row) -> const ZT* { return p64 + row * a.Lp; };
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  uint32_t* hs = reinterpret_cast<uint32_t*>(smem);  // kQW x kHRow words, two u16 counters per word
-  const int lane = threadIdx.x, g = lane >> 4, j = lane & 15;
-  const int blk = blockIdx.x, xcd = blk & 7, slot = blk >> 3;
-  const int chunk = xcd + 8 * (slot / a.nqb);
-  const int qb = slot % a.nqb;
-  if (chunk >= a.nchunks) return;
-  const int64_t c_begin = (int64_t)chunk * a.chunk_len;
-  int64_t c_end = c_begin + a.chunk_len;
-  if (c_end > a.S) c_end = a.S;
-  const int q0 = qb * kQW;
-  for (int i = lane; i < kQW * kHRow; i += 64) hs[i] = 0u;
-
-  ZT qf[4][KS];
-  double qA[4], qB[4], qQ[4], qm[4];
-  int qz = 0, qv = 0;
-#pragma unroll
-  for (int b = 0; b < 4; ++b) {
-    const int q = q0 + 16 * b + j;
-    const bool v = q < a.Q;
-    const ZT* zr = zrow(a.Zq, a.Zq32, v ? q : 0) + g * KS;
-#pragma unroll
-    for (int t = 0; t < KS; ++t) qf[b][t] = v ? zr[t] : (ZT)0;
-    const double* st = a.Sq + (int64_t)(v ? q : 0) * a.nseg * 4;
-    qm[b] = st[0];
-    qA[b] = (0.6 * a.inv_m) * st[1];
-    qB[b] = 0.6 * st[0];
-    qQ[b] = st[2];
-    if (v) qv |= 1 << b;
-    if (st[1] == 0.0) qz |= 1 << b;
-  }
-  __syncthreads();
-  typedef double dbl2v __attribute__((ext_vector_type(2)));
-  auto load_frag = [&](int64_t cs, ZT* dst) {
-    int64_t i = cs + j;
-    if (i >= c_end) i = c_end - 1;
-    const ZT* p = zrow(a.Zc, a.Zc32, i * a.stride) + g * KS;
-#pragma unroll
-    for (int t = 0; t < KS; ++t) dst[t] = p[t];
-  };
-  ZT cf[KS];
-  load_frag(c_begin, cf);
-  for (int64_t cs = c_begin; cs < c_end; cs += kCS) {
-    double cst[12];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      int64_t i = cs + Z::row(g, r);
-      if (i >= c_end) i = c_end - 1;
-      const double* st = a.Sc + i * a.stride * a.nseg * 4;
-      const dbl2v v = *reinterpret_cast<const dbl2v*>(st);
-      cst[3 * r] = v.x;
-      cst[3 * r + 1] = v.y;
-      cst[3 * r + 2] = st[2];
-    }
-    ZT cfn[KS];
-    load_frag(cs + kCS, cfn);
-    AccT acc[4];
-#pragma unroll
-    for (int b = 0; b < 4; ++b) acc[b] = AccT{0, 0, 0, 0};
-#pragma unroll
-    for (int t = 0; t < KS; ++t)
-#pragma unroll
-      for (int b = 0; b < 4; ++b) acc[b] = Z::mfma(cf[t], qf[b][t], acc[b]);  // 4 interleaved chains
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      if (cs + Z::row(g, r) >= c_end) continue;
-      const double cm = cst[3 * r], csd = cst[3 * r + 1], cq = cst[3 * r + 2];
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        if (!((qv >> b) & 1)) continue;
-        const bool zq = (qz >> b) & 1, zc = csd == 0.0;
-        const double sc = (zq || zc) ? const0(zq, zc, qm[b], cm)
-                                     : approx0((double)acc[b][r], a.c1, qA[b], qB[b], qQ[b], csd, cm, cq);
-        int bin = (int)(sc * (double)kBins);
-        bin = bin < 0 ? 0 : (bin >= kBins ? kBins - 1 : bin);
-        atomicAdd(&hs[(16 * b + j) * kHRow + (bin >> 1)], 1u << (16 * (bin & 1)));
-      }
-    }
-#pragma unroll
-    for (int t = 0; t < KS; ++t) cf[t] = cfn[t];
-  }
-  __syncthreads();
-  flush_hist_top(hs, q0, a.Q, a.K, a.hist);
-}
-#endif  // HQ_DIAG
 
 // ------------------------------------------------------------------------------------------------
 // Split-f16 level-0 scan (default).  On gfx950 the f32/f64 MFMAs run on the vector ALUs (they never
@@ -1302,7 +902,11 @@ __global__ __launch_bounds__(64) void k_sample_hist(SampleArgs a) {
 // ------------------------------------------------------------------------------------------------
 constexpr float kMarginF = 6e-5f;
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-constexpr int kPad0 = 3 * kCS;  // pad rows of the f32 copies (hq_seg_pack0_split); k_scan0f reads reach cs + 47
+// Pad rows of the split copies (hq_seg_pack0_split).  The scan and the sample pass read whole 16-row steps
+// with the prefetch index clamped to the chunk's last step, so they reach at most row N + 14; the three
+// steps of padding date from a scan that prefetched two unclamped steps past a chunk.  The value is part of
+// the buffer layout (resident and appended corpora are sized with it), so it stays.
+constexpr int kPad0 = 3 * kCS;
 // rows of the split statistics S32 (SoA groups of 4 rows, padded)
 __host__ __device__ __forceinline__ int64_t pack0_rows(int64_t N) { return ((N + 3) & ~int64_t(3)) + kPad0; }
 // Tiled split fragments Z16 (hq_seg_pack0_split): rows in tiles of 16; tile T = [hi: 64 x 8 halves]
@@ -1335,29 +939,15 @@ __device__ __forceinline__ float lower_f32(double x) {  // largest float <= x (x
   }
   return f;
 }
-__device__ __forceinline__ int shr1_f32i(float v) { return shr1_i32(__float_as_int(v)); }
 
-// One wave = 64 queries (4 blocks b of 16: lane (g, j) owns queries 16b + j) x one corpus chunk,
-// 16 candidates per step (lane group g owns rows 4g + r, r < 4, of the step: the MFMA D layout).
-// Candidate statistics come in the SoA-per-4-rows layout of hq_seg_pack0_split (std[4], mean[4],
-// msq[4], flag bits[4] per group of 4 rows), so the filter's packed f32 arithmetic runs over PAIRS OF
-// ROWS (r, r+1) of one query: G2 = acc.xy / acc.zw and the statistics pairs are register pairs, the
-// query constants are splats — no operand moves.  Per pair:
-//   E = base - T = fma(G, c1, 0.35 - T),  num = fma(G, qA cs, qB cm),  d = fma(E, den, num)
-//   pass <=> max(E, d) >= 0   (den = msq_q + msq_c >= 0; see filter_half)
-// T = thl - kMarginF; 0.35 - T is kept per query (k0) and refreshed only when a threshold moves.
-// The step loop is unrolled by two (ping-pong registers for the next step's fragments/statistics),
-// candidate pointers advance by a constant per step.
-// diagnostics knobs of k_scan0f (HQ_SCAN_EXPT: debug counters, phase skips) exist only in a
-// `make DIAG=1` build; the default build compiles them away
-#ifdef HQ_DIAG
-#define HQ_EXPT(a) ((a).expt)
-#else
-#define HQ_EXPT(a) 0
-#endif
-
-// G-only pre-filter threshold of k_scan0f (see the comment at refresh_k0): smallest G that can pass
-// the filter for list threshold t; out of line (rare: called when a threshold moves)
+// G-only pre-filter threshold: the smallest G that can pass the filter for list threshold t.  By
+// Cauchy-Schwarz (num <= sqrt(A^2 G^2 + B^2) sqrt(msq_c)) and AM-GM (den = Q + msq_c >= 2 sqrt(Q msq_c))
+// every approximate score is at most
+//   U(G) = 0.35 + c1 G + sqrt(A^2 G^2 + B^2) / (2 sqrt(Q))      (A = qA, B = qB, Q = qQ)
+// whatever the candidate; U is strictly increasing (c1 = 0.35/m > A / (2 sqrt Q) <= 0.3/m), so a pair
+// can pass the filter only if G >= G* with U(G*) = T' (T' = t - margin - 1e-5 slack for the f32
+// evaluation).  G* is the smaller root of 4Q (R - c1 G)^2 = A^2 G^2 + B^2, R = T' - 0.35 (the
+// larger one has R - c1 G < 0), evaluated in f64 and rounded down.  Out of line (once per query).
 __device__ __noinline__ float gstar0(float t, float qA, float qB, float qQ, float c1f) {
   if (!(t > -__builtin_huge_valf())) return -__builtin_huge_valf();
   if (!(t < __builtin_huge_valf())) return __builtin_huge_valf();
@@ -1372,384 +962,13 @@ __device__ __noinline__ float gstar0(float t, float qA, float qB, float qQ, floa
   return (float)(G - 1e-6 * (1.0 + fabs(G))) - 1e-5f * (1.0f + fabsf((float)G));
 }
 
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_scan0f(Scan0Args a) {
-  constexpr int NB = 4;
-  constexpr int QW = 16 * NB;  // queries per wave
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  float* ls = reinterpret_cast<float*>(smem);         // QW x K approx scores
-  int* li = reinterpret_cast<int*>(ls + QW * a.K);    // QW x K corpus rows
-  const int lane = threadIdx.x, g = lane >> 4, j = lane & 15;
-  const int blk = blockIdx.x, xcd = blk & 7, slot = blk >> 3;
-  const int chunk = xcd + 8 * (slot / a.nqb);
-  const int qb = slot % a.nqb;
-  if (chunk >= a.nchunks) return;
-  const int64_t c_begin = (int64_t)chunk * a.chunk_len;
-  // chunks past the corpus end exist when nchunks * chunk_len (both rounded up) exceeds N by more than
-  // a chunk (small corpora: N = 3000 -> 192 chunks of 16 rows); their prologue loads (rows c_begin ..
-  // c_begin + 31, unclamped) would read past the kPad0 padding rows, so they leave before any load.
-  // Every other chunk reads at most row c_end + 46 < N + kPad0.
-  if (c_begin >= a.N) return;
-  int64_t c_end = c_begin + a.chunk_len;
-  if (c_end > a.N) c_end = a.N;
-  const int q0 = qb * QW;
-  const int K = a.K;
-  const float c1f = (float)a.c1;
-  int cntr[NB] = {};  // pairs offered to the list of query 16b + j (same in the 4 lanes g)
-
-  // queries: fragments, f32 constants, list thresholds (f32, exact list values)
-  half8 qh[NB], ql[NB];  // query fragments: k range [8g, 8g + 8) of the hi and lo halves
-  float qA[NB], qB[NB], qQ[NB], thl[NB], k0[NB], gs[NB];
-  int qsp = 0;  // bit b: query 16b + j is flagged (zero variance / f32-unsafe)
-  int qvb = 0;  // bit b: query 16b + j exists
-#pragma unroll
-  for (int b = 0; b < NB; ++b) {
-    const int q = q0 + 16 * b + j;
-    const bool v = q < a.Q;
-    const int qq = v ? q : 0;
-    const _Float16* zr = a.Zq16 + z16_frag(qq, g);
-    HQ_GUARD(zr, a.Zq16, z16_rows(a.Q) * 64 - kZ16Lo - 8);
-    qh[b] = *reinterpret_cast<const half8*>(zr);
-    ql[b] = *reinterpret_cast<const half8*>(zr + kZ16Lo);
-    const int64_t gq = (int64_t)(qq >> 2) * 16 + (qq & 3);  // SoA-per-4 statistics
-    const float sd = a.Sq32[gq], mn = a.Sq32[gq + 4], ms = a.Sq32[gq + 8];
-    const int fl = __float_as_int(a.Sq32[gq + 12]);
-    qA[b] = (float)(0.6 * a.inv_m) * sd;
-    qB[b] = 0.6f * mn;
-    qQ[b] = ms;
-    if (v && fl != 0) qsp |= 1 << b;
-    if (v) qvb |= 1 << b;
-    double t0 = a.thr0;
-    if (v && a.th0 && a.th0[q] > t0) t0 = a.th0[q];
-    thl[b] = v ? lower_f32(t0) : __builtin_huge_valf();
-  }
-  // k0 = 0.35 - (thl - margin); flagged queries always pass (+inf), absent ones never (-inf).
-  // gs = G-only pre-filter threshold: by Cauchy-Schwarz (num <= sqrt(A^2 G^2 + B^2) sqrt(msq_c)) and
-  // AM-GM (den = Q + msq_c >= 2 sqrt(Q msq_c)) every approximate score is at most
-  //   U(G) = 0.35 + c1 G + sqrt(A^2 G^2 + B^2) / (2 sqrt(Q))      (A = qA, B = qB, Q = qQ)
-  // whatever the candidate; U is strictly increasing (c1 = 0.35/m > A / (2 sqrt Q) <= 0.3/m), so a pair
-  // can pass the filter only if G >= G* with U(G*) = T' (T' = thl - margin - 1e-5 slack for the f32
-  // evaluation).  G* is the smaller root of 4Q (R - c1 G)^2 = A^2 G^2 + B^2, R = T' - 0.35 (the
-  // larger one has R - c1 G < 0), evaluated in f64 and rounded down.
-  auto refresh_k0 = [&](const int b) {
-    k0[b] = ((qvb >> b) & 1) == 0 ? -__builtin_huge_valf()
-                                  : (((qsp >> b) & 1) != 0 ? __builtin_huge_valf() : 0.35f - (thl[b] - kMarginF));
-    gs[b] = ((qvb >> b) & 1) == 0 ? __builtin_huge_valf()
-                                  : (((qsp >> b) & 1) != 0 ? -__builtin_huge_valf() : gstar0(thl[b], qA[b], qB[b], qQ[b], c1f));
-  };
-#pragma unroll
-  for (int b = 0; b < NB; ++b) refresh_k0(b);
-  for (int i = lane; i < QW * K; i += 64) {
-    ls[i] = -__builtin_huge_valf();
-    li[i] = -1;
-  }
-  const bool myq = lane < QW && q0 + lane < a.Q;
-
-  // candidate rows are padded (kPad0, hq_seg_pack0_split): no clamping, rows past c_end are masked
-  // Candidate statistics: the 16 rows of a step are 4 SoA groups = 64 contiguous floats; lane (g, j)
-  // loads float j of group g (one coalesced dword per lane instead of four 16-B loads that 16 lanes
-  // repeat), and the values are broadcast within the 16-lane row by DPP row_newbcast when the full
-  // filter needs them (rbc<k>).  The flag bits come from one ballot over lanes j >= 12.
-  struct CStep {
-    half8 f[2];  // fragment: hi, lo of row cs + j, k range [8g, 8g + 8)
-    float st;    // SoA statistics float j of group g: std[4], mean[4], msq[4], flags[4]
-  };
-  struct SStat {
-    flt4 sd, mn, ms;  // statistics of rows 4g .. 4g + 3
-  };
-  const _Float16* pz = a.Zc16 + z16_frag(c_begin + j, g);  // c_begin: a multiple of 16
-  const float* pst = a.Sc32 + (c_begin / 4 + g) * 16 + j;
-  auto load_step = [&](CStep& c) {
-    HQ_GUARD(pz, a.Zc16, z16_rows(a.N) * 64 - kZ16Lo - 8);  // half8 at pz and pz + kZ16Lo
-    HQ_GUARD(pst, a.Sc32, pack0_rows(a.N) * 4);
-    c.f[0] = *reinterpret_cast<const half8*>(pz);
-    c.f[1] = *reinterpret_cast<const half8*>(pz + kZ16Lo);
-    c.st = *pst;
-    pz += kZ16Tile;
-    pst += kCS * 4;
-  };
-  auto expand = [&](const float st, SStat& x) {
-    x.sd = flt4{rbc<0>(st), rbc<1>(st), rbc<2>(st), rbc<3>(st)};
-    x.mn = flt4{rbc<4>(st), rbc<5>(st), rbc<6>(st), rbc<7>(st)};
-    x.ms = flt4{rbc<8>(st), rbc<9>(st), rbc<10>(st), rbc<11>(st)};
-  };
-  // bit r: row 4g + r flagged (zero variance / f32-unsafe / pad)
-  auto flags = [&](const float st) -> int {
-    return (int)(__ballot(j >= 12 && __float_as_int(st) != 0) >> (16 * g + 12)) & 0xF;
-  };
-  // G of two 16-query blocks: hi.hi + hi.lo + lo.hi, two accumulation chains interleaved
-  auto mfma_half = [&](const int h, const half8* f, flt4* acc) {
-    acc[0] = flt4{0.0f, 0.0f, 0.0f, 0.0f};
-    acc[1] = flt4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-    for (int u = 0; u < 2; ++u) acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(f[0], qh[2 * h + u], acc[u], 0, 0, 0);
-#pragma unroll
-    for (int u = 0; u < 2; ++u) acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(f[0], ql[2 * h + u], acc[u], 0, 0, 0);
-#pragma unroll
-    for (int u = 0; u < 2; ++u) acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(f[1], qh[2 * h + u], acc[u], 0, 0, 0);
-  };
-  // f32 filter of one half; bit 4u + r = pass of pair (query 16(2h+u)+j, row 4g+r).
-  // pass <=> base >= T or base + num / den >= T  <=>  max(E, E den + num) >= 0 with E = base - T
-  // (den > 0; E den + num is one fma, its sign exact).  Flagged candidates, absent queries and rows
-  // past the chunk end are bit masks, applied only when some lane of the wave has a candidate pass
-  // (the common half-step ends after one ballot).
-  auto filter_half = [&](const int h, const flt4* acc, const float st, const int fm, SStat& x, bool& have,
-                         const int rem) -> int {
-    // G-only pre-filter (see gstar0): most half-steps end here after 4 max and 2 compares
-    const float g0 = fmaxf(fmaxf(acc[0].x, acc[0].y), fmaxf(acc[0].z, acc[0].w));
-    const float g1 = fmaxf(fmaxf(acc[1].x, acc[1].y), fmaxf(acc[1].z, acc[1].w));
-    const unsigned long long pre = HQ_EXPT(a) == 8 ? 0ull : __ballot((g0 >= gs[2 * h]) | (g1 >= gs[2 * h + 1]) | (fm != 0));
-    if (HQ_EXPT(a) == 3 && lane == 0) {
-      atomicAdd(a.dbg + 6, 1ull);
-      if (pre) atomicAdd(a.dbg + 5, 1ull);
-    }
-    if (HQ_EXPT(a) != 5 && !pre) return 0;
-    if (HQ_EXPT(a) == 7) return 0;  // diagnostics only: base cost of the step (no full filter, no inserts)
-    if (!have) {
-      expand(st, x);
-      have = true;
-    }
-    const flt2 c1v = {c1f, c1f};
-    flt2 m[4];  // [2u + p]: rows (2p, 2p + 1) of query block 2h + u
-    float mx = -__builtin_huge_valf();
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int b = 2 * h + u;
-      const flt2 K0 = {k0[b], k0[b]}, A2 = {qA[b], qA[b]}, B2 = {qB[b], qB[b]}, Q2 = {qQ[b], qQ[b]};
-#pragma unroll
-      for (int p = 0; p < 2; ++p) {
-        const flt2 G2 = p == 0 ? acc[u].xy : acc[u].zw;
-        const flt2 sd2 = p == 0 ? x.sd.xy : x.sd.zw;
-        const flt2 mn2 = p == 0 ? x.mn.xy : x.mn.zw;
-        const flt2 ms2 = p == 0 ? x.ms.xy : x.ms.zw;
-        const flt2 E = __builtin_elementwise_fma(G2, c1v, K0);
-        const flt2 num = __builtin_elementwise_fma(G2, A2 * sd2, B2 * mn2);
-        const flt2 d = __builtin_elementwise_fma(E, Q2 + ms2, num);
-        const flt2 mm = {fmaxf(E.x, d.x), fmaxf(E.y, d.y)};
-        m[2 * u + p] = mm;
-        mx = fmaxf(mx, fmaxf(mm.x, mm.y));
-      }
-    }
-    if (!__ballot((mx >= 0.0f) | (fm != 0))) return 0;
-    int bits = 0;
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int p = 0; p < 2; ++p)
-        bits |= ((int)(m[2 * u + p].x >= 0.0f) << (4 * u + 2 * p)) | ((int)(m[2 * u + p].y >= 0.0f) << (4 * u + 2 * p + 1));
-    bits |= fm * 0x11;
-    const int nv = rem - 4 * g;  // rows of this lane group inside the chunk
-    const int rowm = nv >= 4 ? 0xF : (nv <= 0 ? 0 : (1 << nv) - 1);
-    const int b0 = 2 * h, b1 = 2 * h + 1;
-    const int qm = (((qvb >> b0) & 1) ? 0x0F : 0) | (((qvb >> b1) & 1) ? 0xF0 : 0);
-    return bits & (rowm * 0x11) & qm;
-  };
-  // List maintenance.  A query's list starts in APPEND mode: passing pairs are appended in parallel
-  // (slot from the ballot, no ordering) while the list has room; the pair that fills it sorts it (rank
-  // sort), sets the query's threshold to its K-th score and switches it to SORTED mode, where later
-  // pairs are merged one at a time.  With the sampled starting thresholds most queries never leave
-  // append mode within a chunk.  cntr[b] counts the pairs ever offered (>= K: sorted mode); the slots
-  // of a batch follow from its ballot (pairs of query j sit in lanes j, j+16, j+32, j+48).
-  auto key_better = [](float s1, int i1, float s2, int i2) { return s1 > s2 || (s1 == s2 && i1 < i2); };
-  // rank sort of the first n (<= K <= 64) entries of list qi, in place
-  auto sort_list = [&](const int qi, const int n) {
-    float e = lane < n ? ls[qi * K + lane] : -__builtin_huge_valf();
-    int ei = lane < n ? li[qi * K + lane] : 0x7FFFFFFF;
-    int rank = 0;
-    for (int o = 0; o < n; ++o) {
-      const float so = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(e), o));
-      const int io = __builtin_amdgcn_readlane(ei, o);
-      rank += key_better(so, io, e, ei) ? 1 : 0;
-    }
-    if (lane < n) {
-      ls[qi * K + rank] = e;
-      li[qi * K + rank] = ei;
-    }
-  };
-  // raise query qi's threshold to tau (lanes holding it) and publish it
-  auto raise = [&](const int qi, const float tau) {
-    const int b = qi >> 4;
-    if (j == (qi & 15)) {
-#pragma unroll
-      for (int bb = 0; bb < NB; ++bb)
-        if (bb == b && tau > thl[bb]) {
-          thl[bb] = tau;
-          refresh_k0(bb);
-        }
-    }
-    if (lane == 0 && tau > 0.0f) atomicMax(a.gtau + q0 + qi, (unsigned long long)__double_as_longlong((double)tau));
-  };
-  // merge one pair into the sorted list qi
-  auto merge_one = [&](const int qi, const float sc, const int id) {
-    float es = lane < K ? ls[qi * K + lane] : -__builtin_huge_valf();
-    int ei = lane < K ? li[qi * K + lane] : -1;
-    const bool bt = key_better(es, ei, sc, id);
-    const int p = __popcll(__ballot(bt));
-    if (p >= K) return;
-    const float us = __int_as_float(shr1_f32i(es));
-    const int ui = shr1_i32(ei);
-    if (lane > p) { es = us; ei = ui; }
-    if (lane == p) { es = sc; ei = id; }
-    if (lane < K) {
-      ls[qi * K + lane] = es;
-      li[qi * K + lane] = ei;
-    }
-    raise(qi, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(es), K - 1)));
-  };
-  // score, test and file the passing pairs of one half: f32 for plain pairs (the filter's expression
-  // with the division), f64 statistics for flagged pairs
-  auto insert_half = [&](const int h, const flt4* acc, const SStat& c, const int fm, const int64_t cs,
-                         const int bits) {
-    if (HQ_EXPT(a) == 3 && lane == 0) atomicAdd(a.dbg, 1ull);
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int b = 2 * h + u;
-        const bool pb = (bits >> (4 * u + r)) & 1;
-        const unsigned long long mpb = __ballot(pb);
-        if (!mpb) continue;
-        if (HQ_EXPT(a) == 3 && lane == 0) {
-          atomicAdd(a.dbg + 3, (unsigned long long)__popcll(mpb));
-          atomicAdd(a.dbg + 4, 1ull);
-        }
-        float s = -__builtin_huge_valf();
-        const bool flagged = (((qsp >> b) & 1) != 0) | (((fm >> r) & 1) != 0);
-        if (pb && !flagged) {
-          const float G = acc[u][r];
-          const float num = fmaf(G, qA[b] * c.sd[r], qB[b] * c.mn[r]);
-          float t = num * __builtin_amdgcn_rcpf(qQ[b] + c.ms[r]);  // 1 ulp
-          t = t > 0.0f ? t : 0.0f;
-          s = fmaf(G, c1f, 0.35f) + t;
-          s = s < 1.0f ? s : 1.0f;
-          s = s > 0.0f ? s : 0.0f;
-        }
-        if (__ballot(pb && flagged)) {
-          if (pb && flagged) {
-            const int q = q0 + 16 * b + j;
-            const double* sq = a.Sq + (int64_t)q * a.nseg * 4;
-            const double* sc = a.Sc + (cs + 4 * g + r) * a.nseg * 4;
-            HQ_GUARD(sq, a.Sq, (int64_t)a.Q * a.nseg * 4 - 3);
-            HQ_GUARD(sc, a.Sc, a.N * a.nseg * 4 - 3);
-            const double qm = sq[0], qs = sq[1], qq = sq[2], cm = sc[0], csd = sc[1], cq = sc[2];
-            const double v = (qs == 0.0 || csd == 0.0)
-                                 ? const0(qs == 0.0, csd == 0.0, qm, cm, (aux_bits(sq) & aux_bits(sc) & kAuxF32) != 0)
-                                 : approx0((double)acc[u][r], a.c1, (0.6 * a.inv_m) * qs, 0.6 * qm, qq, csd, cm, cq);
-            s = (float)v;
-          }
-        }
-        const bool ok = pb && s >= thl[b];
-        const int qi = 16 * b + j;
-        const int id = (int)(cs + 4 * g + r);
-        const unsigned long long mok = __ballot(ok);
-        if (HQ_EXPT(a) == 3 && lane == 0) atomicAdd(a.dbg + 1, (unsigned long long)__popcll(mok));
-        const unsigned long long mine = (mok >> j) & 0x0001000100010001ull;  // query j's pairs, bit 16g
-        const int pos = cntr[b] + __popcll(mine & ((1ull << (16 * g)) - 1ull));
-        cntr[b] += __popcll(mine);
-        if (ok && pos < K) {
-          ls[qi * K + pos] = s;
-          li[qi * K + pos] = id;
-        }
-        // lists that just filled: sort, threshold
-        unsigned long long mf = __ballot(ok && pos == K - 1);
-        while (mf) {
-          const int l = __builtin_ctzll(mf);
-          mf &= mf - 1;
-          const int qf = 16 * b + (l & 15);
-          sort_list(qf, K);
-          raise(qf, ls[qf * K + K - 1]);
-        }
-        // pairs offered to sorted lists
-        unsigned long long mo = __ballot(ok && pos >= K);
-        if (HQ_EXPT(a) == 3 && lane == 0) atomicAdd(a.dbg + 2, (unsigned long long)__popcll(mo));
-        while (mo) {
-          const int l = __builtin_ctzll(mo);
-          mo &= mo - 1;
-          const float sc = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s), l));
-          const int qo = 16 * b + (l & 15);
-          if (!(sc >= ls[qo * K + K - 1])) continue;
-          merge_one(qo, sc, __builtin_amdgcn_readlane(id, l));
-        }
-      }
-  };
-
-  // Software pipeline: the MFMAs of one half run while the VALU filters the other half
-  //   block A: MFMA(step i, half 1)   || filter(step i, half 0)
-  //   block B: MFMA(step i+1, half 0) || filter(step i, half 1)
-  // Three step buffers: body(i) loads step i + 2 (two bodies of latency cover, the next step's
-  // fragments used by this body's second MFMA half were loaded one body earlier)
-  CStep cA, cB, cC;
-  load_step(cA);
-  load_step(cB);
-  flt4 acc0[2], acc1[2];
-  mfma_half(0, cA.f, acc0);
-  unsigned long long gt_bits = 0ull;
-  int step = 0;
-  auto body = [&](const int64_t cs, const CStep& cur, const CStep& nxt, CStep& nn) {
-    load_step(nn);  // rows past the chunk (padded array, kPad0 rows): harmless, masked
-    const int rem = (int)(c_end - cs);
-    mfma_half(1, cur.f, acc1);
-    const int fm = flags(cur.st);
-    SStat x;
-    bool have = false;
-    const int bits0 = filter_half(0, acc0, cur.st, fm, x, have, rem);
-    if (__ballot(bits0 != 0)) insert_half(0, acc0, x, fm, cs, bits0);
-    mfma_half(0, nxt.f, acc0);
-    const int bits1 = filter_half(1, acc1, cur.st, fm, x, have, rem);
-    if (__ballot(bits1 != 0)) insert_half(1, acc1, x, fm, cs, bits1);
-    if ((step & 3) == 0) {
-      if (gt_bits != 0ull) {
-        const float gf = (float)__longlong_as_double((long long)gt_bits);  // exact: list values are f32
-#pragma unroll
-        for (int b = 0; b < NB; ++b) {
-          const float v = __shfl(gf, 16 * b + j, 64);
-          if (v > thl[b]) {
-            thl[b] = v;
-            refresh_k0(b);
-          }
-        }
-      }
-      if (myq) gt_bits = __atomic_load_n(a.gtau + q0 + lane, __ATOMIC_RELAXED);
-    }
-    ++step;
-  };
-  int64_t cs = c_begin;
-  for (; cs + 2 * kCS < c_end; cs += 3 * kCS) {
-    body(cs, cA, cB, cC);
-    body(cs + kCS, cB, cC, cA);
-    body(cs + 2 * kCS, cC, cA, cB);
-  }
-  if (cs < c_end) body(cs, cA, cB, cC);
-  if (cs + kCS < c_end) body(cs + kCS, cB, cC, cA);
-
-  // hand the lists (unordered is fine) to the per-query pools: one atomic per query, lane-parallel
-  int nl = 0;  // entries of query `lane`
-#pragma unroll
-  for (int b = 0; b < NB; ++b) {
-    const int v = __shfl(cntr[b], lane & 15, 64);
-    if ((lane >> 4) == b) nl = v < K ? v : K;
-  }
-  int base = 0;
-  if (nl > 0 && myq) base = atomicAdd(a.pool_n + q0 + lane, nl);
-  for (int ql = 0; ql < QW; ++ql) {
-    const int n = __builtin_amdgcn_readlane(nl, ql);
-    if (n == 0 || q0 + ql >= a.Q) continue;
-    const int bq = __builtin_amdgcn_readlane(base, ql);
-    if (lane < n && bq + lane < a.pool_cap) {  // (pools hold nchunks x k entries for k <= 64: never past)
-      const int64_t o = (int64_t)(q0 + ql) * a.pool_cap + bq + lane;
-      a.pool_s[o] = ls[ql * K + lane];
-      a.pool_i[o] = li[ql * K + lane];
-    }
-  }
-}
-
 // ------------------------------------------------------------------------------------------------
-// Level-0 scan, queue form (k_scan0g, default since round 3).  Same contraction as k_scan0f (split
-// f16, 12 MFMAs per 64 queries x 16 rows) and the same filter and score expressions, reorganised so
-// that the per-step vector work fits under the matrix instructions:
+// Level-0 scan, queue form (k_scan0g).  The filter and score expressions above, organised so that the
+// per-step vector work fits under the matrix instructions:
 //   * no per-wave lists: a pair whose score passes the query's starting threshold (the sampled bound,
 //     k_sample_kth, or the caller's threshold) is appended straight to the query's global pool, which
 //     k_pool_select reduces to the exact top K (the sample bound admits ~K' x stride pairs per query);
-//   * the per-query constants (QConst, computed once per query by k_sample_kth / k_scan_qprep) leave
+//   * the per-query constants (QConst, computed once per query by k_sample_kth) leave
 //     only the G-only pre-filter in the step: two v_max3 and one compare per 16-query block and lane;
 //   * a lane block (one query, four rows) passing the pre-filter is appended to a per-wave LDS queue
 //     (ballot + mbcnt); the queue is drained 64 entries at a time, one entry per lane: candidate
@@ -1787,20 +1006,6 @@ __device__ __forceinline__ QConst qconst_vals(float sd, float mn, float ms, int 
     c.low = (0.1f >= c.thl - kMarginF) ? 1.0f : 0.0f;
   }
   return c;
-}
-__device__ __forceinline__ QConst qconst_of(const float* Sq32, int q, double t0, double inv_m, float c1f) {
-  const int64_t gq = (int64_t)(q >> 2) * 16 + (q & 3);  // SoA-per-4 statistics
-  (void)c1f;
-  return qconst_vals(Sq32[gq], Sq32[gq + 4], Sq32[gq + 8], __float_as_int(Sq32[gq + 12]), t0, inv_m);
-}
-
-// one thread per query: QConst from the caller's threshold alone (no sample pass)
-__global__ void k_scan_qprep(const float* __restrict__ Sq32, int Q, double thr0, double inv_m,
-                             QConst* __restrict__ qc, int* __restrict__ pool_n) {
-  const int q = blockIdx.x * blockDim.x + threadIdx.x;
-  if (q >= Q) return;
-  qc[q] = qconst_of(Sq32, q, thr0, inv_m, 0.0f);
-  pool_n[q] = 0;
 }
 
 // max of an accumulator in two instructions: IEEE-2019 maximum (v_maximum3_f32 on gfx950; the accumulators
@@ -1892,48 +1097,45 @@ __device__ __noinline__ void stage_flush(StEntry* st, int* scnt, int* sbase, int
   wave_lds_sync();
 }
 
-// WPB waves per workgroup: the WPB waves of a block take WPB consecutive query blocks of ONE chunk and
-// read the same candidate fragments step by step (a barrier per unrolled iteration keeps them within
-// a few steps of each other, so WPB - 1 of the WPB reads of a fragment hit the CU's L1)
-// NB 16-query blocks per wave (4: 64 queries; 8: 128 queries, half the corpus fragment loads per MFMA at
-// more VGPRs), processed as NB / 2 parts of two blocks, software-pipelined: part p's MFMAs are issued
-// before part p - 1's pre-filter reads its accumulators
-// HI (default): the pre-filter contracts hi.hi only (one MFMA per 16 x 16 tile instead of three, the corpus
-// lo fragments are not loaded): |G_split - G_hihi| <= sum |hq lc| + |lq hc| + f32 accumulation
-// < 2^-10 (1.002) m + 1e-5 m, so a lane block passes when max G_hihi >= G* - (1e-3 m + 1e-4); the drain then
-// recomputes each queued block's split G (split_g4) for the filter and the pool score.  HI = false: the
-// three-MFMA form (option scan_split3).
-// OCC: waves per SIMD the register allocation targets (at most 4 since the pool-append stage: 9.7 KB of LDS
-// per wave)
-template <int WPB, int PF, int NB = 4, bool HI = true, int OCC = 5>
-__global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(NB == 8 ? 3 : (HI ? (OCC < 4 ? OCC : 4) : 1)))) void k_scan0g(Scan0Args a) {
-  constexpr int QW = 16 * NB, NP = NB / 2;
-  using QE = QEntry;  // G_hh kept for the drain's gate (QEntryHI: no gate, measured slower)
-  __shared__ QE qe_all[WPB][kQCap];
-  __shared__ StEntry st_all[WPB][kStCap];
-  __shared__ int scnt_all[WPB][QW], sbase_all[WPB][QW];
+// One wave per workgroup, 64 queries per wave as four 16-query blocks, processed as two parts of two blocks,
+// software-pipelined: part p's MFMAs are issued before part p - 1's pre-filter reads its accumulators.
+// The pre-filter contracts hi.hi only (one MFMA per 16 x 16 tile instead of three, the corpus lo fragments
+// are not loaded): |G_split - G_hihi| <= sum |hq lc| + |lq hc| + f32 accumulation < 2^-10 (1.002) m + 1e-5 m,
+// so a lane block passes when max G_hihi >= G* - (1e-3 m + 1e-4); the drain then recomputes each queued
+// block's split G (split_g4) for the filter and the pool score.
+// 3 waves per SIMD (168 VGPRs: room for the 6-step prefetch; the stage and queue take 9.7 KB of LDS per
+// wave), one round of 3072 waves (scan0_geometry): the list-1008 scan 197 -> 161 us against 4 waves per SIMD
+// with a 4-step prefetch (the round-6 occupancy A/B under profiles/).
+constexpr int kScanPF = 6;  // prefetch distance of k_scan0g, steps
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void k_scan0g(Scan0Args a) {
+  constexpr int NB = 4, QW = 16 * NB, NP = NB / 2, PF = kScanPF;
+  static_assert(QW == kQW, "scan0_geometry counts query blocks of kQW");
+  __shared__ QEntry qe_all[kQCap];
+  __shared__ StEntry st_all[kStCap];
+  __shared__ int scnt_all[QW], sbase_all[QW];
+  QEntry* qe = qe_all;
+  StEntry* st = st_all;
+  int* scnt = scnt_all;
+  int* sbase = sbase_all;
   const int lane = threadIdx.x & 63, g = lane >> 4, j = lane & 15;
-  QE* qe = qe_all[WPB > 1 ? threadIdx.x >> 6 : 0];
-  StEntry* st = st_all[WPB > 1 ? threadIdx.x >> 6 : 0];
-  int* scnt = scnt_all[WPB > 1 ? threadIdx.x >> 6 : 0];
-  int* sbase = sbase_all[WPB > 1 ? threadIdx.x >> 6 : 0];
   for (int t = lane; t < QW; t += 64) scnt[t] = 0;
   const int blk = blockIdx.x, xcd = blk & 7, slot = blk >> 3;
-  const int nqg = (a.nqb + WPB - 1) / WPB;
-  const int chunk = xcd + 8 * (slot / nqg);
-  const int qb = (slot % nqg) * WPB + (WPB > 1 ? (int)(threadIdx.x >> 6) : 0);
+  const int chunk = xcd + 8 * (slot / a.nqb);
+  const int qb = slot % a.nqb;
   if (chunk >= a.nchunks) return;
   const int64_t c_begin = (int64_t)chunk * a.chunk_len;
-  if (c_begin >= a.N) return;  // chunks past the corpus end (k_scan0f comment)
+  // chunks past the corpus end exist when nchunks * chunk_len (both rounded up) exceeds N by more than a
+  // chunk (small corpora: N = 3000 -> 192 chunks of 16 rows); they leave before any load
+  if (c_begin >= a.N) return;
   int64_t c_end = c_begin + a.chunk_len;
   if (c_end > a.N) c_end = a.N;
   const int q0 = qb * QW;
   const float c1f = (float)a.c1;
   const QConst* qc = reinterpret_cast<const QConst*>(a.qconst);
 
-  half8 qh[NB], ql[HI ? 1 : NB];
+  half8 qh[NB];
   float gs[NB];
-  const float dG = HI ? (float)(1e-3 / a.inv_m) + 1e-4f : 0.0f;  // hi.hi pre-filter slack (above)
+  const float dG = (float)(1e-3 / a.inv_m) + 1e-4f;  // hi.hi pre-filter slack (above)
 #pragma unroll
   for (int b = 0; b < NB; ++b) {
     const int q = q0 + 16 * b + j;
@@ -1942,39 +1144,24 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(NB == 
     const _Float16* zr = a.Zq16 + z16_frag(qq, g);
     HQ_GUARD(zr, a.Zq16, z16_rows(a.Q) * 64 - kZ16Lo - 8);
     qh[b] = *reinterpret_cast<const half8*>(zr);
-    if constexpr (!HI) ql[b] = *reinterpret_cast<const half8*>(zr + kZ16Lo);
     gs[b] = v ? qc[q].gs - dG : __builtin_huge_valf();
   }
 
   // wave-uniform bases, per-lane constant offsets (scalar step increments)
   const char* zb = reinterpret_cast<const char*>(a.Zc16 + (c_begin >> 4) * kZ16Tile);  // c_begin: a multiple of 16
   const int zoff = lane * 16;  // bytes: the lane's 8 halves of a tile
-  struct CStep {
-    half8 f[HI ? 1 : 2];
-  };
-#ifdef HQ_DIAG
-  const int64_t smul = (a.expt == 5 || a.expt == 6) ? 0 : kZ16Tile * 2;  // timing experiments: step 0 only
-#else
   constexpr int64_t smul = kZ16Tile * 2;
-#endif
+  struct CStep { half8 f; };  // the hi fragment of a step
   auto load_step = [&](CStep& c, const int64_t s) {
     const _Float16* p = reinterpret_cast<const _Float16*>(zb + s * smul + zoff);
     HQ_GUARD(p, a.Zc16, z16_rows(a.N) * 64 - kZ16Lo - 8);
-    c.f[0] = *reinterpret_cast<const half8*>(p);
-    if constexpr (!HI) c.f[HI ? 0 : 1] = *reinterpret_cast<const half8*>(p + kZ16Lo);
+    c.f = *reinterpret_cast<const half8*>(p);
   };
-  auto mfma_part = [&](const int h, const half8* f, flt4* acc) {
+  auto mfma_part = [&](const int h, const half8& f, flt4* acc) {
     acc[0] = flt4{0.0f, 0.0f, 0.0f, 0.0f};
     acc[1] = flt4{0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
-    for (int u = 0; u < 2; ++u) acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(f[0], qh[2 * h + u], acc[u], 0, 0, 0);
-    if constexpr (!HI) {
-#pragma unroll
-      for (int u = 0; u < 2; ++u) acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(f[0], ql[2 * h + u], acc[u], 0, 0, 0);
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-        acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(f[HI ? 0 : 1], qh[2 * h + u], acc[u], 0, 0, 0);
-    }
+    for (int u = 0; u < 2; ++u) acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(f, qh[2 * h + u], acc[u], 0, 0, 0);
   };
 
   int qn = 0;  // queue entries (wave-uniform)
@@ -1997,27 +1184,24 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(NB == 
       const flt4 mn = *reinterpret_cast<const flt4*>(stt + 4);
       const flt4 ms = *reinterpret_cast<const flt4*>(stt + 8);
       const flt4 fl = *reinterpret_cast<const flt4*>(stt + 12);
-      bool need = true;
-      if constexpr (HI) {
-        // gate: the filter is monotone in G and G_split <= G_hh + dG, so a block none of whose rows passes at
-        // G_hh + dG needs no split recompute (most queued blocks: the G-only pre-filter is looser)
-        need = false;
+      // gate: the filter is monotone in G and G_split <= G_hh + dG, so a block none of whose rows passes at
+      // G_hh + dG needs no split recompute (most queued blocks: the G-only pre-filter is looser)
+      bool need = false;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float Gu = eg[r] + dG;
-          const float E = fmaf(Gu, c1f, c.k0);
-          const float d = fmaf(E, c.qQ + ms[r], fmaf(Gu, c.qA * sd[r], c.qB * mn[r]));
-          need |= erow + r < c_end && __float_as_int(fl[r]) == 0 && fmaxf(E, d) >= 0.0f;
-        }
-        if (need) eg = split_g4(a.Zq16, a.Zc16, q, erow);
+      for (int r = 0; r < 4; ++r) {
+        const float Gu = eg[r] + dG;
+        const float E = fmaf(Gu, c1f, c.k0);
+        const float d = fmaf(E, c.qQ + ms[r], fmaf(Gu, c.qA * sd[r], c.qB * mn[r]));
+        need |= erow + r < c_end && __float_as_int(fl[r]) == 0 && fmaxf(E, d) >= 0.0f;
       }
+      if (need) eg = split_g4(a.Zq16, a.Zc16, q, erow);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int row = erow + r;
         const int f = __float_as_int(fl[r]);
         if (!need || row >= c_end || f != 0) continue;  // past the chunk; flagged rows: k_pool_select
         const float G = eg[r];
-        // division-free filter (k_scan0f filter_half), then the list score (k_scan0f insert_half)
+        // division-free filter, then the list score (the expressions at the head of this section)
         const float E = fmaf(G, c1f, c.k0);
         const float num = fmaf(G, c.qA * sd[r], c.qB * mn[r]);
         const float d = fmaf(E, c.qQ + ms[r], num);
@@ -2099,10 +1283,6 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(NB == 
   // pre-filter of one half: max of the lane's four rows per block against G* (the compare's lane mask
   // is the ballot); blocks holding a flagged row (f32-unsafe; zero-variance for a query that admits 0.1)
   // are queued regardless
-#ifdef HQ_DIAG
-  if (a.expt == 6)  // timing experiment: nothing is queued
-    for (int b = 0; b < NB; ++b) gs[b] = __builtin_huge_valf();
-#endif
   auto part_step = [&](const int h, const flt4* acc, const int64_t cs) {
     const unsigned long long m0 = __builtin_amdgcn_ballot_w64(max4(acc[0]) >= gs[2 * h]);
     const unsigned long long m1 = __builtin_amdgcn_ballot_w64(max4(acc[1]) >= gs[2 * h + 1]);
@@ -2120,29 +1300,22 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(NB == 
   for (int u = 0; u < PF; ++u) load_step(buf[u], u < nsteps ? u : nsteps - 1);
   flt4 acc[NP][2];
   mfma_part(0, buf[0].f, acc[0]);
-#ifdef HQ_DIAG
-  // timing experiments: 7 = no pre-filter (loads + MFMAs only), 9 = no loads after the prologue
-  const bool x_nofilter = a.expt == 7, x_noload = a.expt == 9;
-#else
-  constexpr bool x_nofilter = false, x_noload = false;
-#endif
   auto body = [&](const int64_t s, const CStep& cur, const CStep& nxt, CStep& nn) {
-    if (!x_noload) load_step(nn, s + PF < nsteps ? s + PF : nsteps - 1);
+    load_step(nn, s + PF < nsteps ? s + PF : nsteps - 1);
     __builtin_amdgcn_sched_barrier(0);  // keep the prefetch PF steps ahead (the scheduler sinks it otherwise)
     const int64_t cs = c_begin + s * kCS;
 #pragma unroll
     for (int p = 1; p < NP; ++p) {
       mfma_part(p, cur.f, acc[p]);
-      if (!x_nofilter) part_step(p - 1, acc[p - 1], cs);
+      part_step(p - 1, acc[p - 1], cs);
     }
     mfma_part(0, nxt.f, acc[0]);
-    if (!x_nofilter) part_step(NP - 1, acc[NP - 1], cs);
+    part_step(NP - 1, acc[NP - 1], cs);
   };
   int64_t s = 0;
   for (; s + PF < nsteps; s += PF + 1) {
 #pragma unroll
     for (int u = 0; u <= PF; ++u) body(s + u, buf[u], buf[(u + 1) % (PF + 1)], buf[(u + PF) % (PF + 1)]);
-    if constexpr (WPB > 1) __builtin_amdgcn_s_barrier();  // same step count in every wave of the block
   }
 #pragma unroll
   for (int u = 0; u < PF; ++u)
@@ -2164,8 +1337,8 @@ __global__ __launch_bounds__(256) void k_flag_rows(const float* __restrict__ S32
     flag_row(S32, r, list, count);
 }
 
-// one flagged row against one scanned query: the f64 statistics as k_scan0f's insert
-// path (const0 for zero variance, approx0 with G from the split copies otherwise), appended to the pools
+// one flagged row against one scanned query, from the f64 statistics (const0 for zero variance, approx0 with
+// G from the split copies otherwise), appended to the pools
 // when the score reaches the query's list threshold
 __device__ __forceinline__ void flagged_pair(const Scan0Args& a, const QConst& c, int q, int row) {
   const double* sq = a.Sq + (int64_t)q * a.nseg * 4;
@@ -2214,7 +1387,7 @@ __global__ __launch_bounds__(64) void k_pool_select(float* pool_s, int* pool_i, 
                                                     const int* __restrict__ fcount) {
   const int lane = threadIdx.x;
   for (int q = blockIdx.x; q < Q; q += gridDim.x) {
-    // fcount != null (k_scan0g): the corpus's flagged rows against this query first (lanes over the
+    // fcount != null (the level-0 scan): the corpus's flagged rows against this query first (lanes over the
     // rows), appended to the pool before it is read; pool_n is then read with an
     // L1-bypassing load (the appends are L2 atomics)
     // the flagged-row count, the pool count and the query's flag word are requested together (one round
@@ -2385,271 +1558,21 @@ __global__ __launch_bounds__(64) void k_pool_select(float* pool_s, int* pool_i, 
   }
 }
 
-#ifdef HQ_DIAG
-// f32 sample pass: f32 scores of a strided subset into per-query histograms; flagged pairs are not
-// counted (which only lowers the bound)
-__global__ __launch_bounds__(64) void k_sample_histf(SampleArgs a) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  uint32_t* hs = reinterpret_cast<uint32_t*>(smem);  // kQW x kHRow words, two u16 counters per word
-  const int lane = threadIdx.x, g = lane >> 4, j = lane & 15;
-  const int blk = blockIdx.x, xcd = blk & 7, slot = blk >> 3;
-  const int chunk = xcd + 8 * (slot / a.nqb);
-  const int qb = slot % a.nqb;
-  if (chunk >= a.nchunks) return;
-  const int64_t c_begin = (int64_t)chunk * a.chunk_len;
-  int64_t c_end = c_begin + a.chunk_len;
-  if (c_end > a.S) c_end = a.S;
-  const int q0 = qb * kQW;
-  const float c1f = (float)a.c1;
-  for (int i = lane; i < kQW * kHRow; i += 64) hs[i] = 0u;
-
-  half8 qh[4], ql[4];
-  float qA[4], qB[4], qQ[4];
-  int qok = 0;  // bit b: valid, unflagged query
-#pragma unroll
-  for (int b = 0; b < 4; ++b) {
-    const int q = q0 + 16 * b + j;
-    const bool v = q < a.Q;
-    const int qq = v ? q : 0;
-    const _Float16* zr = a.Zq16 + z16_frag(qq, g);
-    qh[b] = *reinterpret_cast<const half8*>(zr);
-    ql[b] = *reinterpret_cast<const half8*>(zr + kZ16Lo);
-    const int64_t gq = (int64_t)(qq >> 2) * 16 + (qq & 3);  // SoA-per-4 statistics
-    qA[b] = (float)(0.6 * a.inv_m) * a.Sq32[gq];
-    qB[b] = 0.6f * a.Sq32[gq + 4];
-    qQ[b] = a.Sq32[gq + 8];
-    if (v && __float_as_int(a.Sq32[gq + 12]) == 0) qok |= 1 << b;
-  }
-  __syncthreads();
-  auto row_of = [&](int64_t i) -> int64_t { return sample_row_tiled(i, a.S, a.stride); };
-  auto load_frag = [&](int64_t cs, half8* dst) {
-    const _Float16* p = a.Zc16 + z16_frag(row_of(cs + j), g);
-    HQ_GUARD(p, a.Zc16, z16_rows(a.N) * 64 - kZ16Lo - 8);
-    dst[0] = *reinterpret_cast<const half8*>(p);
-    dst[1] = *reinterpret_cast<const half8*>(p + kZ16Lo);
-  };
-  half8 cf[2];
-  load_frag(c_begin, cf);
-  float cut[4] = {-1.0f, -1.0f, -1.0f, -1.0f};  // per query: scores below need no counting
-  int step = 0;
-  for (int64_t cs = c_begin; cs < c_end; cs += kCS) {
-    flt4 cst[4];  // (std, mean, msq, flags) of rows 4g + r
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int64_t row = row_of(cs + 4 * g + r);
-      const float* p = a.Sc32 + (row >> 2) * 16 + (row & 3);
-      cst[r] = flt4{p[0], p[4], p[8], p[12]};
-    }
-    half8 cfn[2];
-    load_frag(cs + kCS, cfn);
-    flt4 acc[4];
-#pragma unroll
-    for (int b = 0; b < 4; ++b) acc[b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(cf[0], qh[b], flt4{0, 0, 0, 0}, 0, 0, 0);
-#pragma unroll
-    for (int b = 0; b < 4; ++b) acc[b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(cf[0], ql[b], acc[b], 0, 0, 0);
-#pragma unroll
-    for (int b = 0; b < 4; ++b) acc[b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(cf[1], qh[b], acc[b], 0, 0, 0);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const bool ok = cs + 4 * g + r < c_end && __float_as_int(cst[r].w) == 0;
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        const float G = acc[b][r];
-        // division-free test against the cut first (most pairs stop here)
-        const float R = cut[b] - fmaf(G, c1f, 0.35f);
-        const float num = fmaf(G, qA[b] * cst[r].x, qB[b] * cst[r].y);
-        const float den = qQ[b] + cst[r].z;
-        if (!ok || !((qok >> b) & 1) || !((R <= 0.0f) || (num >= R * den))) continue;
-        float t = num * __builtin_amdgcn_rcpf(den);
-        t = t > 0.0f ? t : 0.0f;
-        const float sc = fmaf(G, c1f, 0.35f) + t;
-        int bin = (int)(sc * (float)kBins);
-        bin = bin < 0 ? 0 : (bin >= kBins ? kBins - 1 : bin);
-        atomicAdd(&hs[(16 * b + j) * kHRow + (bin >> 1)], 1u << (16 * (bin & 1)));
-      }
-    }
-    cf[0] = cfn[0];
-    cf[1] = cfn[1];
-    // every 8 steps: cut = lower edge of the bin holding this wave's K-th best score of each query;
-    // lower bins would never be flushed (flush_hist_top stops at K), so they need not be counted
-    if ((++step & 7) == 0) {
-      const uint32_t* hq = hs + lane * kHRow;
-      unsigned int cum = 0;
-      int e = -1;
-      for (int w = kBins / 2 - 1; w >= 0; --w) {
-        const uint32_t v = hq[w];
-        cum += v >> 16;
-        if (cum >= (unsigned)a.K) { e = 2 * w + 1; break; }
-        cum += v & 0xFFFFu;
-        if (cum >= (unsigned)a.K) { e = 2 * w; break; }
-      }
-      const float cv = e > 0 ? (float)e / (float)kBins - 1e-6f : -1.0f;
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        const float v = __shfl(cv, 16 * b + j, 64);
-        cut[b] = v > cut[b] ? v : cut[b];
-      }
-    }
-  }
-  __syncthreads();
-  flush_hist_top(hs, q0, a.Q, a.K, a.hist);
-}
-#endif  // HQ_DIAG
-
-// f32 sample pass, top-T form (default): no histogram.  Every lane (g, j) keeps, for each of its
-// four queries 16b + j, the kTopT best approximate scores of its own stream of sample rows (rows 4g ..
-// 4g + 3 of every step of its chunk), tested division-free against its own kTopT-th best.  The values
-// of all streams are real scores of distinct (query, row) pairs, so the K-th best of their union
-// (k_sample_kth) is a lower bound of the K-th best over the sample and hence over the corpus; it is
-// as tight as the sample's own K-th unless a stream held more than kTopT of the sample's top K.
+// Sample pass: a strided subset of the corpus (whole tiles, sample_row_tiled) is scored with the scan's
+// contraction and score expression.  Every lane (g, j) keeps, for each of its four queries 16b + j, up to
+// kTopT approximate scores of its own stream of sample rows (rows 4g .. 4g + 3 of every step of its chunk).
+// The values of all streams are real scores of distinct (query, row) pairs, so the K-th best of their union
+// (k_sample_kth) is a lower bound of the K-th best over the sample and hence over the corpus.
 // No LDS, no atomics: occupancy is set by VGPRs alone.  Output: top[(q * nstreams + 4 chunk + g) *
 // kTopT + t], every entry of every existing query written (-1 = empty).
 constexpr int kTopT = 2;
 
-__global__ __launch_bounds__(64) void k_sample_topf(SampleArgs a) {
-  const int lane = threadIdx.x, g = lane >> 4, j = lane & 15;
-  const int blk = blockIdx.x, xcd = blk & 7, slot = blk >> 3;
-  const int chunk = xcd + 8 * (slot / a.nqb);
-  const int qb = slot % a.nqb;
-  if (chunk >= a.nchunks) return;
-  const int64_t c_begin = (int64_t)chunk * a.chunk_len;
-  int64_t c_end = c_begin + a.chunk_len;
-  if (c_end > a.S) c_end = a.S;
-  const int q0 = qb * kQW;
-  const float c1f = (float)a.c1;
-
-  half8 qh[4], ql[4];
-  float qA[4], qB[4], qQ[4];
-  int qok = 0;  // bit b: valid, unflagged query
-#pragma unroll
-  for (int b = 0; b < 4; ++b) {
-    const int q = q0 + 16 * b + j;
-    const bool v = q < a.Q;
-    const int qq = v ? q : 0;
-    const _Float16* zr = a.Zq16 + z16_frag(qq, g);
-    qh[b] = *reinterpret_cast<const half8*>(zr);
-    ql[b] = *reinterpret_cast<const half8*>(zr + kZ16Lo);
-    const int64_t gq = (int64_t)(qq >> 2) * 16 + (qq & 3);  // SoA-per-4 statistics
-    qA[b] = (float)(0.6 * a.inv_m) * a.Sq32[gq];
-    qB[b] = 0.6f * a.Sq32[gq + 4];
-    qQ[b] = a.Sq32[gq + 8];
-    if (v && __float_as_int(a.Sq32[gq + 12]) == 0) qok |= 1 << b;
-  }
-  float top[4][kTopT];
-#pragma unroll
-  for (int b = 0; b < 4; ++b)
-#pragma unroll
-    for (int t = 0; t < kTopT; ++t) top[b][t] = -1.0f;
-  // k0[b] = 0.35 - (current kTopT-th best); +inf-free: an invalid / flagged query never passes
-  float k0[4];
-#pragma unroll
-  for (int b = 0; b < 4; ++b) k0[b] = ((qok >> b) & 1) ? 1.35f : -__builtin_huge_valf();
-  auto row_of = [&](int64_t i) -> int64_t { return sample_row_tiled(i, a.S, a.stride); };
-  auto load_frag = [&](int64_t cs, half8* dst) {
-    const _Float16* p = a.Zc16 + z16_frag(row_of(cs + j), g);
-    HQ_GUARD(p, a.Zc16, z16_rows(a.N) * 64 - kZ16Lo - 8);
-    dst[0] = *reinterpret_cast<const half8*>(p);
-    dst[1] = *reinterpret_cast<const half8*>(p + kZ16Lo);
-  };
-  // statistics: lane (g, j) loads stat (j & 3) (std, mean, msq, flags) of row 4g + (j >> 2) - one dword
-  // per lane - and the 16 values of the lane group are broadcast by DPP row_newbcast
-  auto load_stats = [&](int64_t cs) -> float {
-    const int64_t row = row_of(cs + 4 * g + (j >> 2));
-    const float* p = a.Sc32 + (row >> 2) * 16 + (j & 3) * 4 + (row & 3);
-    HQ_GUARD(p, a.Sc32, pack0_rows(a.N) * 4);  // sample tiles may end in pad rows (flag 4: not scored)
-    return *p;
-  };
-  // fragments and statistics are loaded two steps ahead (3-buffer rotation, as in k_scan0f): at 2 waves
-  // per SIMD one step of strided-row latency was exposed per step
-  half8 cf[2], cf1[2];
-  load_frag(c_begin, cf);
-  float stv = load_stats(c_begin);
-  load_frag(c_begin + kCS, cf1);
-  float st1 = load_stats(c_begin + kCS);
-  for (int64_t cs = c_begin; cs < c_end; cs += kCS) {
-    half8 cfn[2];
-    load_frag(cs + 2 * kCS, cfn);
-    const float stn = load_stats(cs + 2 * kCS);
-    const flt4 cst[4] = {flt4{rbc<0>(stv), rbc<1>(stv), rbc<2>(stv), rbc<3>(stv)},
-                         flt4{rbc<4>(stv), rbc<5>(stv), rbc<6>(stv), rbc<7>(stv)},
-                         flt4{rbc<8>(stv), rbc<9>(stv), rbc<10>(stv), rbc<11>(stv)},
-                         flt4{rbc<12>(stv), rbc<13>(stv), rbc<14>(stv), rbc<15>(stv)}};
-    flt4 acc[4];
-#pragma unroll
-    for (int b = 0; b < 4; ++b) acc[b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(cf[0], qh[b], flt4{0, 0, 0, 0}, 0, 0, 0);
-#pragma unroll
-    for (int b = 0; b < 4; ++b) acc[b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(cf[0], ql[b], acc[b], 0, 0, 0);
-#pragma unroll
-    for (int b = 0; b < 4; ++b) acc[b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(cf[1], qh[b], acc[b], 0, 0, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    // division-free test against the lane's own kTopT-th best: score > t <=> max(E, E den + num) > 0
-    int bits = 0;  // bit 4b + r
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const bool ok = cs + 4 * g + r < c_end && __float_as_int(cst[r].w) == 0;
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        const float G = acc[b][r];
-        const float E = fmaf(G, c1f, k0[b]);
-        const float num = fmaf(G, qA[b] * cst[r].x, qB[b] * cst[r].y);
-        const float d = fmaf(E, qQ[b] + cst[r].z, num);
-        bits |= (int)(ok && fmaxf(E, d) > 0.0f) << (4 * b + r);
-      }
-    }
-    if (__ballot(bits != 0)) {
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          if ((bits >> (4 * b + r)) & 1) {
-            const float G = acc[b][r];
-            const float num = fmaf(G, qA[b] * cst[r].x, qB[b] * cst[r].y);
-            float t = num * __builtin_amdgcn_rcpf(qQ[b] + cst[r].z);
-            t = t > 0.0f ? t : 0.0f;
-            float sc = fmaf(G, c1f, 0.35f) + t;
-            sc = sc < 1.0f ? sc : 1.0f;
-            sc = sc > 0.0f ? sc : 0.0f;  // +0 for -0 and negatives (k_sample_kth orders bit patterns)
-            // sorted insert (descending), branch-free
-#pragma unroll
-            for (int u = 0; u < kTopT; ++u) {
-              const float hi = fmaxf(top[b][u], sc);
-              sc = fminf(top[b][u], sc);
-              top[b][u] = hi;
-            }
-          }
-        }
-        k0[b] = ((qok >> b) & 1) ? 0.35f - top[b][kTopT - 1] : -__builtin_huge_valf();
-      }
-    }
-    cf[0] = cf1[0];
-    cf[1] = cf1[1];
-    cf1[0] = cfn[0];
-    cf1[1] = cfn[1];
-    stv = st1;
-    st1 = stn;
-  }
-  const int ns = 4 * a.nchunks;
-#pragma unroll
-  for (int b = 0; b < 4; ++b) {
-    const int q = q0 + 16 * b + j;
-    if (q >= a.Q) continue;
-    float* o = a.top + ((int64_t)q * ns + 4 * chunk + g) * kTopT;
-#pragma unroll
-    for (int t = 0; t < kTopT; ++t) o[t] = top[b][t];
-  }
-}
-
-// f32 sample pass, G-selected form (default): the step loop keeps, per lane (g, j) and query block b,
-// only the step whose four rows 4g .. 4g + 3 hold the largest G (two v_max, one compare and six
+// G-selected: the step loop (the split contraction, three MFMAs per block) keeps, per lane (g, j) and query
+// block b, only the step whose four rows 4g .. 4g + 3 hold the largest G (two v_max, one compare and six
 // v_cndmask per block and step: the MFMA work sets the pace, as in k_scan0g), and scores the rows of
-// that step exactly (f32 model) at the end; the stream's kTopT best of those scores go to the pool.  They
-// are real scores of distinct (query, row) pairs, so the K-th best of the union is still a lower bound of
-// the K-th best over the corpus (selecting by G instead of by score only makes it less tight).  Query
-// constants and candidate statistics are read in the epilogue alone.  HI (default): the step loop
-// contracts hi.hi only (the kept step is a heuristic choice) and the epilogue recomputes the kept rows'
-// split G (split_g4) for the model score.
-template <bool HI = true>
+// that step exactly (f32 model) at the end; the stream's kTopT best of those scores go to the pool
+// (selecting by G instead of by score only makes the bound less tight).  Query constants and candidate
+// statistics are read in the epilogue alone.
 __global__ __launch_bounds__(64) void k_sample_topg(SampleArgs a) {
   const int lane = threadIdx.x, g = lane >> 4, j = lane & 15;
   const int blk = blockIdx.x, xcd = blk & 7, slot = blk >> 3;
@@ -2666,14 +1589,14 @@ __global__ __launch_bounds__(64) void k_sample_topg(SampleArgs a) {
     const int q = q0 + 16 * b + j;
     const _Float16* zr = a.Zq16 + z16_frag(q < a.Q ? q : 0, g);
     qh[b] = *reinterpret_cast<const half8*>(zr);
-    if constexpr (!HI) ql[b] = *reinterpret_cast<const half8*>(zr + kZ16Lo);
+    ql[b] = *reinterpret_cast<const half8*>(zr + kZ16Lo);
   }
   auto row_of = [&](int64_t i) -> int64_t { return sample_row_tiled(i, a.S, a.stride); };
   auto load_frag = [&](int64_t cs, half8* dst) {
     const _Float16* p = a.Zc16 + z16_frag(row_of(cs + j), g);
     HQ_GUARD(p, a.Zc16, z16_rows(a.N) * 64 - kZ16Lo - 8);
     dst[0] = *reinterpret_cast<const half8*>(p);
-    if constexpr (!HI) dst[1] = *reinterpret_cast<const half8*>(p + kZ16Lo);
+    dst[1] = *reinterpret_cast<const half8*>(p + kZ16Lo);
   };
   float bg[4];     // largest max-of-four G so far
   flt4 bacc[4];    // G of that step's four rows
@@ -2693,12 +1616,10 @@ __global__ __launch_bounds__(64) void k_sample_topg(SampleArgs a) {
     flt4 acc[4];
 #pragma unroll
     for (int b = 0; b < 4; ++b) acc[b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(cf[0], qh[b], flt4{0, 0, 0, 0}, 0, 0, 0);
-    if constexpr (!HI) {
 #pragma unroll
-      for (int b = 0; b < 4; ++b) acc[b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(cf[0], ql[b], acc[b], 0, 0, 0);
+    for (int b = 0; b < 4; ++b) acc[b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(cf[0], ql[b], acc[b], 0, 0, 0);
 #pragma unroll
-      for (int b = 0; b < 4; ++b) acc[b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(cf[1], qh[b], acc[b], 0, 0, 0);
-    }
+    for (int b = 0; b < 4; ++b) acc[b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(cf[1], qh[b], acc[b], 0, 0, 0);
     if (cs + kCS > c_end) {  // the chunk's last, partial step: rows past c_end never win
 #pragma unroll
       for (int r = 0; r < 4; ++r)
@@ -2716,10 +1637,8 @@ __global__ __launch_bounds__(64) void k_sample_topg(SampleArgs a) {
     }
     cf[0] = cf1[0];
     cf1[0] = cfn[0];
-    if constexpr (!HI) {
-      cf[1] = cf1[1];
-      cf1[1] = cfn[1];
-    }
+    cf[1] = cf1[1];
+    cf1[1] = cfn[1];
   }
   // epilogue: exact f32 model scores of the selected rows, the stream's kTopT best to the pool.  Every
   // statistic is requested before any is used (one round trip): the four rows a lane scores per block are rows
@@ -2753,8 +1672,7 @@ __global__ __launch_bounds__(64) void k_sample_topg(SampleArgs a) {
 #pragma unroll
     for (int t = 0; t < kTopT; ++t) top[t] = -1.0f;
     if (qok && bcs[b] >= 0) {
-      flt4 Gs = bacc[b];
-      if constexpr (HI) Gs = split_g4(a.Zq16, a.Zc16, q, row_of((int64_t)bcs[b] + 4 * g));  // 4 consecutive rows
+      const flt4 Gs = bacc[b];
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int64_t i = (int64_t)bcs[b] + 4 * g + r;
@@ -2786,20 +1704,16 @@ __global__ __launch_bounds__(64) void k_sample_topg(SampleArgs a) {
 // bits + 1, 0 = empty), th0 = v - margin, or -inf when fewer than K sample scores exist
 constexpr int kKthReg = 32;  // pool entries per lane: 4 * 256 chunks * kTopT / 64
 
-// Also clears the scan's per-query published threshold and pool count (gtau, pool_n; top-T mode has no
-// histogram, so no memset runs before the scan).
+// Also clears the scan's per-query pool count (pool_n), so no memset runs before the scan.
 template <int R>
 __global__ __launch_bounds__(64) void k_sample_kth(const float* __restrict__ top, int ns, int Q, int K, double margin,
-                                                   double* __restrict__ th0, unsigned long long* __restrict__ gtau,
+                                                   double* __restrict__ th0,
                                                    int* __restrict__ pool_n, const float* __restrict__ Sq32, double thr0,
                                                    double inv_m, QConst* __restrict__ qc) {
   const int lane = threadIdx.x;
   const int P = ns * kTopT;
   for (int q = blockIdx.x; q < Q; q += gridDim.x) {
-    if (lane == 0) {
-      if (gtau) gtau[q] = 0ull;
-      pool_n[q] = 0;
-    }
+    if (lane == 0) pool_n[q] = 0;
     const float* p = top + (int64_t)q * P;
     // the query's statistics for its constants, requested with the pool (one round trip)
     float st[4] = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -2840,38 +1754,19 @@ __global__ __launch_bounds__(64) void k_sample_kth(const float* __restrict__ top
 // the pool held in registers: R = 8 / 16 / 32 entries per lane (ns * kTopT <= 64 R; the geometry caps it
 // at 64 kKthReg), so a smaller pool makes every bisection step cheaper
 static void launch_kth(int mg, hipStream_t s, const float* top, int ns, int Q, int K, double margin, double* th0,
-                       unsigned long long* gtau, int* pool_n, const float* Sq32, double thr0, double inv_m,
+                       int* pool_n, const float* Sq32, double thr0, double inv_m,
                        QConst* qc) {
   const int P = ns * kTopT;
   if (P <= 64 * 8)
-    hipLaunchKernelGGL(k_sample_kth<8>, dim3(mg), dim3(64), 0, s, top, ns, Q, K, margin, th0, gtau, pool_n, Sq32, thr0,
+    hipLaunchKernelGGL(k_sample_kth<8>, dim3(mg), dim3(64), 0, s, top, ns, Q, K, margin, th0, pool_n, Sq32, thr0,
                        inv_m, qc);
   else if (P <= 64 * 16)
-    hipLaunchKernelGGL(k_sample_kth<16>, dim3(mg), dim3(64), 0, s, top, ns, Q, K, margin, th0, gtau, pool_n, Sq32,
+    hipLaunchKernelGGL(k_sample_kth<16>, dim3(mg), dim3(64), 0, s, top, ns, Q, K, margin, th0, pool_n, Sq32,
                        thr0, inv_m, qc);
   else
-    hipLaunchKernelGGL(k_sample_kth<kKthReg>, dim3(mg), dim3(64), 0, s, top, ns, Q, K, margin, th0, gtau, pool_n, Sq32,
+    hipLaunchKernelGGL(k_sample_kth<kKthReg>, dim3(mg), dim3(64), 0, s, top, ns, Q, K, margin, th0, pool_n, Sq32,
                        thr0, inv_m, qc);
 }
-
-#ifdef HQ_DIAG
-// per-query starting threshold from the sample histogram (-inf when the sample has < K scores)
-__global__ void k_hist_tau(const unsigned int* __restrict__ hist, int Q, int K, double margin,
-                           double* __restrict__ th0) {
-  const int q = blockIdx.x * blockDim.x + threadIdx.x;
-  if (q >= Q) return;
-  unsigned int cum = 0;
-  double t = -__builtin_huge_val();
-  for (int e = kBins - 1; e >= 0; --e) {
-    cum += hist[(int64_t)q * kBins + e];
-    if (cum >= (unsigned int)K) {
-      t = (double)e / (double)kBins - margin;  // margin > the score error of the sample pass
-      break;
-    }
-  }
-  th0[q] = t;
-}
-#endif  // HQ_DIAG
 
 // merge nchunks sorted lists per query (one wave per query)
 __global__ __launch_bounds__(64) void k_merge(const double* __restrict__ ws_score, const int64_t* __restrict__ ws_id,
@@ -3460,9 +2355,9 @@ __device__ __forceinline__ double overall_from_levels(const double* lv, const in
   VecSet Qs, int Q, VecSet Cs, int64_t N, SegInfo si, int mode, const double *__restrict__ cs,                  \
       const int64_t *__restrict__ cid, int kp, int k, double thr, int thr_mode, double eps, int64_t id_base,     \
       double *__restrict__ os, int64_t *__restrict__ oid, int *__restrict__ ocnt, int *__restrict__ ores,        \
-      int count_empty, int *__restrict__ oredo, double *__restrict__ odet, int expt,     \
+      int count_empty, int *__restrict__ oredo, double *__restrict__ odet,               \
       int *__restrict__ onext
-#define HQ_REFINE_PASS Qs, Q, Cs, N, si, mode, cs, cid, kp, k, thr, thr_mode, eps, id_base, os, oid, ocnt, ores, count_empty, oredo, odet, expt, onext
+#define HQ_REFINE_PASS Qs, Q, Cs, N, si, mode, cs, cid, kp, k, thr, thr_mode, eps, id_base, os, oid, ocnt, ores, count_empty, oredo, odet, onext
 template <bool SM>
 __device__ __forceinline__ void refine_lds_body(HQ_REFINE_ARGS) {
   if (onext && blockIdx.x == 0 && threadIdx.x == 0) *onext = 0;  // the next batch's redo counter
@@ -3491,7 +2386,7 @@ __device__ __forceinline__ void refine_lds_body(HQ_REFINE_ARGS) {
     }
     __syncthreads();
     // stage by LDS-DMA (global_load_lds_dwordx4: lane l writes 16 B at m0 + 16 l), all pieces in flight
-    for (int r = wave; r < nr && expt != 1; r += 4) {  // expt: diagnostics (1 no staging, 2 no scoring)
+    for (int r = wave; r < nr; r += 4) {
       const int64_t i = srow[r];
       if (i < 0) continue;
       if (r == 0) {
@@ -3507,7 +2402,7 @@ __device__ __forceinline__ void refine_lds_body(HQ_REFINE_ARGS) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     // level scores: task t = s * kp + p
-    for (int t = tid; t < nlev * kp && expt != 2; t += 256) {
+    for (int t = tid; t < nlev * kp; t += 256) {
       const int sg = t / kp, p = t - sg * kp;
       double v = 0.0;
       int f32 = 0;
@@ -4574,13 +3469,13 @@ struct FinalOut {
   int64_t* id;
   double* det;
   int* count;
-  int rounds;  // 1: K <= kFinalRounds outputs by arg-max rounds where cheaper than the sort (option final_rounds)
+  int rounds;  // 1: K <= kFinalRounds outputs by arg-max rounds where cheaper than the sort
 };
 
 
 // (round 6: a register-resident form — two entries per thread, in-wave partners by lane shuffles, LDS only
 // across waves, NT = n2 / 2 — measured slower, 97.5 -> 121 us at M = 1000 and 20.8 -> 28.2 us at M = 100:
-// profiles/r06_ab_scan_occ.txt; not kept)
+// the round-6 occupancy A/B under profiles/; not kept)
 // CAP: list entries the workgroup holds (a power of two >= kp): kMaxTopKBig, or 128 for the M = 100 lists
 // (4 KB of LDS per workgroup instead of 33: many queries per CU)
 template <int NT, int CAP = kMaxTopKBig>
@@ -5187,13 +4082,11 @@ static void scan_geometry(int Q, int64_t N, int& nqb, int& nchunks, int64_t& chu
   if (chunk_len < kCB) chunk_len = kCB;
 }
 
-// k_scan0: ~16 resident waves per CU-pair of rounds; nchunks multiple of 8 (XCD mapping), <= 512
-static void scan0_geometry(int Q, int64_t N, int& nqb, int& nchunks, int64_t& chunk_len, int qw = kQW, int occ = 4) {
-  nqb = (Q + qw - 1) / qw;
-  // ~4096 waves of 64 queries (4 per SIMD); 128-query waves (k_scan0g<.., 8>, 3 per SIMD): one round of 3072;
-  // occ 3 (option scan_occ 3: 64-query waves at 3 per SIMD, deeper prefetch): one round of 3072
-  const int64_t waves = qw <= kQW ? (occ == 3 ? 3072LL : 4096LL * (kQW / qw)) : 3072;
-  int64_t target = (waves + nqb - 1) / nqb;
+// grid of k_scan0g: one round of 3072 waves of 64 queries (3 per SIMD); nchunks a multiple of 8 (XCD mapping),
+// <= 512, chunks of whole 16-row steps
+static void scan0_geometry(int Q, int64_t N, int& nqb, int& nchunks, int64_t& chunk_len) {
+  nqb = (Q + kQW - 1) / kQW;
+  int64_t target = (3072 + nqb - 1) / nqb;
   int64_t max_chunks = (N + kCS - 1) / kCS;
   if (target > max_chunks) target = max_chunks;
   if (target > 512) target = 512;
@@ -5204,16 +4097,17 @@ static void scan0_geometry(int Q, int64_t N, int& nqb, int& nchunks, int64_t& ch
   if (chunk_len < kCS) chunk_len = kCS;
 }
 
-// top-T sample pass (k_sample_topf): same stride rule as the histogram pass; ~2048 waves (no per-wave
-// setup cost, so more waves only add occupancy), chunks a multiple of 8 (XCD map) and of kCS rows
+// sample stride: 16 once the corpus is large, else a sample of ~4096 rows (the whole corpus below that)
+static int64_t sampling_stride(int64_t N) { return N >= 16 * 4096 ? 16 : (N / 4096 > 1 ? N / 4096 : 1); }
+
+// grid of k_sample_topg: ~2048 waves (no per-wave setup cost, so more waves only add occupancy), chunks a
+// multiple of 8 (XCD map) and of kCS rows
 static void sample_top_geometry(int Q, int64_t N, int64_t& stride, int64_t& S, int& nqb, int& nchunks,
                                 int64_t& chunk_len) {
-  const int64_t sd = opt(OPT_SAMPLE_STRIDE, 16) > 0 ? opt(OPT_SAMPLE_STRIDE, 16) : 16;  // A/B option
-  stride = N >= sd * 4096 ? sd : (N / 4096 > 1 ? N / 4096 : 1);
-  S = sample_rows_tiled(N, stride);  // whole 16-row tiles (k_sample_topf)
+  stride = sampling_stride(N);
+  S = sample_rows_tiled(N, stride);  // whole 16-row tiles
   nqb = (Q + kQW - 1) / kQW;
-  const int waves = opt(OPT_SAMPLE_WAVES, 2048) > 0 ? (int)opt(OPT_SAMPLE_WAVES, 2048) : 2048;
-  int64_t target = (waves + nqb - 1) / nqb;
+  int64_t target = (2048 + nqb - 1) / nqb;
   const int64_t max_chunks = (S + kCS - 1) / kCS;
   if (target > max_chunks) target = max_chunks;
   if (target > 64 * kKthReg / (4 * kTopT)) target = 64 * kKthReg / (4 * kTopT);  // k_sample_kth pool in registers
@@ -5265,8 +4159,8 @@ static int pool_cap_for(int nchunks, int k, int64_t N, int64_t stride, int kprim
   return (int)(c < n64 ? c : n64);
 }
 
-static size_t scan0_lists_bytes(int Q, int64_t N, int k, int nchunks) {
-  if (k <= kMaxTopK) return (size_t)nchunks * Q * k * 16;
+// the pools of all queries: scores (f32) then rows (i32), pool_cap_for entries each
+static size_t scan0_pools_bytes(int Q, int64_t N, int k, int nchunks) {
   int64_t stride, S, chunk_len;
   int nqb, sn;
   sample_top_geometry(Q, N, stride, S, nqb, sn, chunk_len);
@@ -5274,306 +4168,74 @@ static size_t scan0_lists_bytes(int Q, int64_t N, int k, int nchunks) {
   return (b + 255) & ~(size_t)255;
 }
 
+// workspace of the level-0 scan: [pools][th0 Q x 8][pool_n Q x 4][sample tops][QConst table, 256-B aligned]
+// [flagged-row count and list, 256-B aligned]
 static size_t scan0_ws_bytes(int Q, int64_t N, int k) {
-  int nqb, nchunks, nqb2, nchunks2;
-  int64_t chunk_len, chunk_len2;
+  int nqb, nchunks;
+  int64_t chunk_len;
   scan0_geometry(Q, N, nqb, nchunks, chunk_len);
-  scan0_geometry(Q, N, nqb2, nchunks2, chunk_len2, 32);
-  if (nchunks2 > nchunks) nchunks = nchunks2;
-  if (opt(OPT_SCAN_NB, 4) == 8) {  // the 128-query scan's geometry (A/B option) only when selected
-    scan0_geometry(Q, N, nqb2, nchunks2, chunk_len2, 128);
-    if (nchunks2 > nchunks) nchunks = nchunks2;
-  }
-  // lists / pools + global thresholds + sample histogram + starting thresholds + pool counts + sample tops
-  return scan0_lists_bytes(Q, N, k, nchunks) + (size_t)Q * 8 + (size_t)Q * kBins * 4 + (size_t)Q * 8 + (size_t)Q * 4 +
-         sample_top_bytes(Q, N) + (size_t)Q * sizeof(QConst) + (size_t)N * 4 + 1024;
+  return scan0_pools_bytes(Q, N, k, nchunks) + (size_t)Q * 8 + (size_t)Q * 4 + sample_top_bytes(Q, N) +
+         (size_t)Q * sizeof(QConst) + (size_t)N * 4 + 1024;
 }
 
-#ifdef HQ_DIAG
-// sample pass: stride 16 once the corpus is large, else a sample of ~4096 rows (the whole corpus
-// below that); chunks of <= 65520 rows (u16 histogram counters), ~1024 waves (a wave has a fixed
-// cost: histogram init and flush)
-static void sample_geometry(int Q, int64_t N, int64_t& stride, int64_t& S, int& nqb, int& nchunks,
-                            int64_t& chunk_len, bool tiled) {
-  const int64_t sd = opt(OPT_SAMPLE_STRIDE, 16) > 0 ? opt(OPT_SAMPLE_STRIDE, 16) : 16;  // A/B option
-  stride = N >= sd * 4096 ? sd : (N / 4096 > 1 ? N / 4096 : 1);
-  S = tiled ? sample_rows_tiled(N, stride) : (N + stride - 1) / stride;  // f32 (split) samples: whole tiles
-  nqb = (Q + kQW - 1) / kQW;
-  const int waves = opt(OPT_SAMPLE_WAVES, 1024) > 0 ? (int)opt(OPT_SAMPLE_WAVES, 1024) : 1024;
-  int64_t target = (waves + nqb - 1) / nqb;
-  const int64_t max_chunks = (S + kCS - 1) / kCS;
-  if (target > max_chunks) target = max_chunks;
-  if (target < (S + 65519) / 65520) target = (S + 65519) / 65520;
-  nchunks = (int)(((target + 7) / 8) * 8);
-  chunk_len = (S + nchunks - 1) / nchunks;
-  chunk_len = ((chunk_len + kCS - 1) / kCS) * kCS;
-}
-#endif  // HQ_DIAG
-
-static int launch_scan0f(const Scan0Args& a, hipStream_t s) {
-  const size_t lds = (size_t)kQW * a.K * 8;
-  HQ_CHECK_HIP(hipFuncSetAttribute((const void*)k_scan0f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(k_scan0f, dim3(a.nqb * a.nchunks), dim3(64), lds, s, a);
-  HQ_CHECK_LAUNCH();
-  return HQ_OK;
-}
-
-#ifdef HQ_DIAG
-template <int KS, bool F32>
-static int launch_sample(const SampleArgs& a, hipStream_t s) {
-  const size_t lds = (size_t)kQW * kHRow * 4;
-  const void* fn = F32 ? (const void*)k_sample_histf : (const void*)k_sample_hist<KS>;
-  HQ_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  if constexpr (F32) hipLaunchKernelGGL(k_sample_histf, dim3(a.nqb * a.nchunks), dim3(64), lds, s, a);
-  else hipLaunchKernelGGL((k_sample_hist<KS>), dim3(a.nqb * a.nchunks), dim3(64), lds, s, a);
-  HQ_CHECK_LAUNCH();
-  return HQ_OK;
-}
-
-template <int KS, bool F32>
-static int launch_scan0(const Scan0Args& a, hipStream_t s) {
-  if constexpr (F32) return launch_scan0f(a, s);
-  const size_t lds = (size_t)kQW * 32 + (size_t)kQW * a.K * 12;
-  HQ_CHECK_HIP(hipFuncSetAttribute((const void*)k_scan0<KS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL((k_scan0<KS>), dim3(a.nqb * a.nchunks), dim3(64), lds, s, a);
-  HQ_CHECK_LAUNCH();
-  return HQ_OK;
-}
-
-template <bool F32>
-static int scan0_dispatch(int ks, const Scan0Args& b, const SampleArgs* sa, hipStream_t s) {
-  int rc;
-  if (sa) {
-    switch (ks) {
-      case 1: rc = launch_sample<1, F32>(*sa, s); break;
-      case 2: rc = launch_sample<2, F32>(*sa, s); break;
-      case 3: rc = launch_sample<3, F32>(*sa, s); break;
-      case 4: rc = launch_sample<4, F32>(*sa, s); break;
-      case 5: rc = launch_sample<5, F32>(*sa, s); break;
-      case 6: rc = launch_sample<6, F32>(*sa, s); break;
-      case 7: rc = launch_sample<7, F32>(*sa, s); break;
-      default: rc = launch_sample<8, F32>(*sa, s); break;
-    }
-    return rc;
-  }
-  switch (ks) {
-    case 1: rc = launch_scan0<1, F32>(b, s); break;
-    case 2: rc = launch_scan0<2, F32>(b, s); break;
-    case 3: rc = launch_scan0<3, F32>(b, s); break;
-    case 4: rc = launch_scan0<4, F32>(b, s); break;
-    case 5: rc = launch_scan0<5, F32>(b, s); break;
-    case 6: rc = launch_scan0<6, F32>(b, s); break;
-    case 7: rc = launch_scan0<7, F32>(b, s); break;
-    default: rc = launch_scan0<8, F32>(b, s); break;
-  }
-  return rc;
-}
-
-#endif  // HQ_DIAG
-
-// level-0 scan: top-T sample pass -> starting thresholds -> k_scan0f -> k_pool_select (split-f16
-// contraction, f32 == true).  DIAG builds keep the superseded forms for A/B: the f64 wave-level scan
-// k_scan0 (f32 == false, merged by k_merge) and the histogram sample pass (option sample_hist).
-static int scan0_run(bool f32, int ks, const double* Zq, const double* Sq, const _Float16* Zq16, const float* Sq32,
-                     int Q, const double* Zc, const double* Sc, const _Float16* Zc16, const float* Sc32, int64_t N,
-                     const SegInfo& si, int k, double threshold, int thr_mode, int64_t id_base, void* workspace,
-                     double* out_score, int64_t* out_id, hipStream_t s, const int* corpus_flags = nullptr) {
-#ifndef HQ_DIAG
-  if (!f32) return fail(HQ_E_UNSUPPORTED, "the f64 level-0 scan exists only in DIAG builds");
-#endif
+// level-0 scan: sample pass -> starting thresholds and per-query constants (k_sample_kth) -> k_scan0g ->
+// k_pool_select
+static int scan0_run(const double* Sq, const _Float16* Zq16, const float* Sq32, int Q, const double* Sc,
+                     const _Float16* Zc16, const float* Sc32, int64_t N, const SegInfo& si, int k, double threshold,
+                     int thr_mode, int64_t id_base, void* workspace, double* out_score, int64_t* out_id, hipStream_t s,
+                     const int* corpus_flags) {
   Scan0Args b;
-  b.Zq = Zq; b.Sq = Sq; b.Q = Q; b.Zc = Zc; b.Sc = Sc; b.N = N;
-  b.Zq32 = nullptr; b.Zc32 = nullptr; b.Zq16 = Zq16; b.Zc16 = Zc16; b.Sq32 = Sq32; b.Sc32 = Sc32;
-  b.Lp = si.Lp; b.nseg = si.nseg; b.P0 = si.plen[0];
+  b.Sq = Sq; b.Q = Q; b.Sc = Sc; b.N = N;
+  b.Zq16 = Zq16; b.Zc16 = Zc16; b.Sc32 = Sc32;
+  b.nseg = si.nseg;
   b.inv_m = si.inv_m[0];
   b.c1 = 0.35 * si.inv_m[0];
-  b.K = k;
-  b.thr0 = thr_mode == 0 ? -__builtin_huge_val() : threshold;
-  b.id_base = id_base;
-  b.expt = 0;
-  b.dbg = nullptr;
-#ifdef HQ_DIAG
-  b.expt = (int)opt(OPT_SCAN_EXPT, 0);
-  static unsigned long long* dbg = nullptr;
-  if (b.expt == 3) {
-    if (!dbg) HQ_CHECK_HIP(hipMalloc(&dbg, 64));
-    HQ_CHECK_HIP(hipMemsetAsync(dbg, 0, 64, s));
-  }
-  b.dbg = dbg;
-#endif
-  // option scan_nb 8: 128-query waves (k_scan0g<1, PF, 8>) and their geometry
-  const int scan_nb = f32 && opt(OPT_SCAN_NB, 4) == 8 && opt(OPT_SCAN_WPB, 1) != 4 ? 8 : 4;
-  // 3 waves per SIMD (default since round 6; 168 VGPRs: room for a 6-step prefetch), 3072 waves: the list-1008
-  // scan 197 -> 161 us (profiles/r06_ab_scan_occ.txt).  Option scan_occ 4: the round-5 form (4 per SIMD, 4 steps)
-  const int socc = f32 && scan_nb == 4 && opt(OPT_SCAN_WPB, 1) != 4 && opt(OPT_SCAN_OCC, 3) == 3 ? 3 : 4;
-  scan0_geometry(Q, N, b.nqb, b.nchunks, b.chunk_len, 16 * scan_nb, socc);
-  uint8_t* ws = reinterpret_cast<uint8_t*>(workspace);
-  b.ws_score = reinterpret_cast<double*>(ws);
-  b.ws_id = reinterpret_cast<int64_t*>(ws + (size_t)b.nchunks * Q * k * 8);
-  // [lists / pools][gtau Q x 8][hist Q x kBins x 4][pool_n Q x 4][th0 Q x 8][sample tops]: the zeroed
-  // regions are adjacent, so one memset clears them
-  const size_t lists = scan0_lists_bytes(Q, N, k, b.nchunks);
-  b.gtau = reinterpret_cast<unsigned long long*>(ws + lists);
-  unsigned int* hist = reinterpret_cast<unsigned int*>(ws + lists + (size_t)Q * 8);
-  b.pool_n = reinterpret_cast<int*>(ws + lists + (size_t)Q * 8 + (size_t)Q * kBins * 4);
-  double* th0 = reinterpret_cast<double*>(ws + lists + (size_t)Q * 8 + (size_t)Q * kBins * 4 + (size_t)Q * 4);
-  b.th0 = nullptr;
-  // f32 path: per-query pools in the list area (pool_cap_for: nchunks * k entries for k <= 64)
-  int64_t s_stride, s_S, s_len;
-  int s_nqb, s_nch;
-  sample_top_geometry(Q, N, s_stride, s_S, s_nqb, s_nch, s_len);
-  b.pool_cap = pool_cap_for(b.nchunks, k, N, s_stride, scan_kprime(k, s_stride));
-  b.pool_s = reinterpret_cast<float*>(ws);
-  b.pool_i = reinterpret_cast<int*>(ws + (size_t)Q * b.pool_cap * 4);
-  // option scan_nosample: no sample pass, the scan starts from the caller's threshold
-  const bool sample = !opt_on(OPT_SCAN_NOSAMPLE);
-  bool top_sample = sample && f32;
-#ifdef HQ_DIAG
-  if (top_sample && opt(OPT_SCAN_VARIANT, 0) == 100) top_sample = false;  // the histogram sample pass
-#endif
+  const double thr0 = thr_mode == 0 ? -__builtin_huge_val() : threshold;  // initial threshold (-inf: none)
+  scan0_geometry(Q, N, b.nqb, b.nchunks, b.chunk_len);
+  SampleArgs sa;
+  sa.Q = Q; sa.N = N; sa.Zq16 = Zq16; sa.Zc16 = Zc16; sa.Sq32 = Sq32; sa.Sc32 = Sc32;
+  sa.inv_m = b.inv_m; sa.c1 = b.c1;
+  sample_top_geometry(Q, N, sa.stride, sa.S, sa.nqb, sa.nchunks, sa.chunk_len);
   // K' of the starting threshold: the sample's K'-th best (statistical for K' < k: pools left short are
   // marked for the exact path, k_pool_select); option sample_kth = 0 -> k (a provable bound)
-  int sample_kth = scan_kprime(k, s_stride);
-  float* top = reinterpret_cast<float*>(ws + lists + (size_t)Q * 8 + (size_t)Q * kBins * 4 + (size_t)Q * 4 +
-                                        (size_t)Q * 8);
-  // k_scan0g (default; option scan_variant 1 = the list-based k_scan0f): per-query constants after the
-  // sample tops, 256-B aligned
-  // (the list kernel keeps one list entry per lane and nchunks x k pool slots: k <= 64 only, so longer
-  // lists always take the queue scan whatever the option says)
-  const bool queue_scan = f32 && (opt(OPT_SCAN_VARIANT, 0) != 1 || k > kMaxTopK);
-  const size_t qc_off = ((size_t)(reinterpret_cast<uint8_t*>(top) - ws) + sample_top_bytes(Q, N) + 255) & ~(size_t)255;
-  QConst* qc = queue_scan ? reinterpret_cast<QConst*>(ws + qc_off) : nullptr;
+  const int sample_kth = scan_kprime(k, sa.stride);
+  uint8_t* ws = reinterpret_cast<uint8_t*>(workspace);
+  const size_t pools = scan0_pools_bytes(Q, N, k, b.nchunks);
+  b.pool_cap = pool_cap_for(b.nchunks, k, N, sa.stride, sample_kth);
+  b.pool_s = reinterpret_cast<float*>(ws);
+  b.pool_i = reinterpret_cast<int*>(ws + (size_t)Q * b.pool_cap * 4);
+  double* th0 = reinterpret_cast<double*>(ws + pools);
+  b.pool_n = reinterpret_cast<int*>(ws + pools + (size_t)Q * 8);
+  sa.top = reinterpret_cast<float*>(ws + pools + (size_t)Q * 8 + (size_t)Q * 4);
+  const size_t qc_off = ((size_t)(reinterpret_cast<uint8_t*>(sa.top) - ws) + sample_top_bytes(Q, N) + 255) & ~(size_t)255;
+  QConst* qc = reinterpret_cast<QConst*>(ws + qc_off);
   b.qconst = qc;
   int* flag_n = reinterpret_cast<int*>(ws + ((qc_off + (size_t)Q * sizeof(QConst) + 255) & ~(size_t)255));
   int* flag_list = flag_n + 64;
-  // (the top-T sample has no histogram and k_sample_kth clears gtau and pool_n per query)
-  if (!top_sample)
-    HQ_CHECK_HIP(hipMemsetAsync(b.gtau, 0, (size_t)Q * 8 + (sample ? (size_t)Q * kBins * 4 : 0) + (f32 ? (size_t)Q * 4 : 0),
-                                s));
-  if (f32 && !sample) HQ_CHECK_HIP(hipMemsetAsync(b.pool_n, 0, sizeof(int) * Q, s));
-  int rc;
-  if (top_sample) {
-    SampleArgs sa;
-    sa.Zq = Zq; sa.Sq = Sq; sa.Q = Q; sa.Zc = Zc; sa.Sc = Sc; sa.N = N;
-    sa.Zq32 = nullptr; sa.Zc32 = nullptr; sa.Zq16 = Zq16; sa.Zc16 = Zc16; sa.Sq32 = Sq32; sa.Sc32 = Sc32;
-    sa.Lp = b.Lp; sa.nseg = b.nseg; sa.P0 = b.P0; sa.inv_m = b.inv_m; sa.c1 = b.c1;
-    sample_top_geometry(Q, N, sa.stride, sa.S, sa.nqb, sa.nchunks, sa.chunk_len);
-    sa.hist = nullptr;
-    sa.top = top;
-    sa.K = k;
-    // option sample_variant 1: the full-filter sample pass (k_sample_topf)
-    if (opt(OPT_SAMPLE_VARIANT, 0) == 1)
-      hipLaunchKernelGGL(k_sample_topf, dim3(sa.nqb * sa.nchunks), dim3(64), 0, s, sa);
-    else if (opt(OPT_SAMPLE_HI, 0) == 1)  // hi.hi step loop + split G epilogue: 58 vs 34 us (the epilogue's loads)
-      hipLaunchKernelGGL(k_sample_topg<true>, dim3(sa.nqb * sa.nchunks), dim3(64), 0, s, sa);
-    else
-      hipLaunchKernelGGL(k_sample_topg<false>, dim3(sa.nqb * sa.nchunks), dim3(64), 0, s, sa);
-    HQ_CHECK_LAUNCH();
-    const int mg = Q < 8192 ? Q : 8192;
-    launch_kth(mg, s, (const float*)top, 4 * sa.nchunks, Q, sample_kth, (double)kMarginF, th0, b.gtau, b.pool_n, Sq32,
-               b.thr0, b.inv_m, qc);
-    HQ_CHECK_LAUNCH();
-    b.th0 = th0;
-  }
-#ifdef HQ_DIAG
-  else if (sample) {
-    SampleArgs sa;
-    sa.top = nullptr;
-    sa.Zq = Zq; sa.Sq = Sq; sa.Q = Q; sa.Zc = Zc; sa.Sc = Sc; sa.N = N;
-    sa.Zq32 = nullptr; sa.Zc32 = nullptr; sa.Zq16 = Zq16; sa.Zc16 = Zc16; sa.Sq32 = Sq32; sa.Sc32 = Sc32;
-    sa.Lp = b.Lp; sa.nseg = b.nseg; sa.P0 = b.P0; sa.inv_m = b.inv_m; sa.c1 = b.c1;
-    sample_geometry(Q, N, sa.stride, sa.S, sa.nqb, sa.nchunks, sa.chunk_len, f32);
-    sa.hist = hist;
-    sa.K = k;
-    rc = f32 ? scan0_dispatch<true>(ks, b, &sa, s) : scan0_dispatch<false>(ks, b, &sa, s);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_hist_tau, dim3((Q + 255) / 256), dim3(256), 0, s, (const unsigned int*)hist, Q, k,
-                       f32 ? (double)kMarginF : 1e-12, th0);
-    HQ_CHECK_LAUNCH();
-    b.th0 = th0;
-  }
-#else
-  (void)hist;
-  rc = HQ_OK;
-#endif
-  if (queue_scan) {
-    if (!top_sample) {  // no sample pass: the constants from the caller's threshold (and pool counts cleared)
-      hipLaunchKernelGGL(k_scan_qprep, dim3((Q + 255) / 256), dim3(256), 0, s, Sq32, Q, b.thr0, b.inv_m, qc, b.pool_n);
-      HQ_CHECK_LAUNCH();
-    }
-    if (corpus_flags) {  // the corpus's flagged rows listed once (hq_seg_flag_rows): [count, rows...]
-      flag_n = const_cast<int*>(corpus_flags);
-      flag_list = flag_n + 1;
-    } else {
-      HQ_CHECK_HIP(hipMemsetAsync(flag_n, 0, sizeof(int), s));
-      const int64_t fb = (N + 255) / 256;
-      hipLaunchKernelGGL(k_flag_rows, dim3((unsigned)(fb < 4096 ? fb : 4096)), dim3(256), 0, s, Sc32, N, flag_list,
-                         flag_n);
-      HQ_CHECK_LAUNCH();
-    }
-    // options scan_wpb: waves per block (1 = one wave per block, each reading its own fragments);
-    // scan_pf: prefetch distance in steps (2, 3, 4, 6, 8; 4 measured best at 4 waves per SIMD: 4.73M vs
-    // 4.64M QPS at 2, 3.02M at 6 where the queue spills)
-    const int pf = (int)opt(OPT_SCAN_PF, socc == 3 ? 6 : 4);
-    if (opt(OPT_SCAN_WPB, 1) == 4) {
-      const dim3 g4((b.nqb + 3) / 4 * b.nchunks);
-      if (pf == 4) hipLaunchKernelGGL((k_scan0g<4, 4>), g4, dim3(256), 0, s, b);
-      else if (pf == 3) hipLaunchKernelGGL((k_scan0g<4, 3>), g4, dim3(256), 0, s, b);
-      else hipLaunchKernelGGL((k_scan0g<4, 2>), g4, dim3(256), 0, s, b);
-    } else {
-      const dim3 g1(b.nqb * b.nchunks);
-      if (scan_nb == 8) hipLaunchKernelGGL((k_scan0g<1, 2, 8>), g1, dim3(64), 0, s, b);
-      else if (opt_on(OPT_SCAN_SPLIT3)) hipLaunchKernelGGL((k_scan0g<1, 2, 4, false>), g1, dim3(64), 0, s, b);
-      else if (opt(OPT_SCAN_OCC, 3) == 5) {
-        if (pf == 4) hipLaunchKernelGGL((k_scan0g<1, 4, 4, true, 5>), g1, dim3(64), 0, s, b);
-        else hipLaunchKernelGGL((k_scan0g<1, 2, 4, true, 5>), g1, dim3(64), 0, s, b);
-      } else if (socc == 3) {
-        if (pf == 8) hipLaunchKernelGGL((k_scan0g<1, 8, 4, true, 3>), g1, dim3(64), 0, s, b);
-        else if (pf == 6) hipLaunchKernelGGL((k_scan0g<1, 6, 4, true, 3>), g1, dim3(64), 0, s, b);
-        else hipLaunchKernelGGL((k_scan0g<1, 4, 4, true, 3>), g1, dim3(64), 0, s, b);
-      } else {  // 4 waves per SIMD (measured best: 4.64M vs 1.41M QPS at 5 with the drain gate)
-        if (pf == 8) hipLaunchKernelGGL((k_scan0g<1, 8, 4, true, 4>), g1, dim3(64), 0, s, b);
-        else if (pf == 6) hipLaunchKernelGGL((k_scan0g<1, 6, 4, true, 4>), g1, dim3(64), 0, s, b);
-        else if (pf == 4) hipLaunchKernelGGL((k_scan0g<1, 4, 4, true, 4>), g1, dim3(64), 0, s, b);
-        else if (pf == 3) hipLaunchKernelGGL((k_scan0g<1, 3, 4, true, 4>), g1, dim3(64), 0, s, b);
-        else hipLaunchKernelGGL((k_scan0g<1, 2, 4, true, 4>), g1, dim3(64), 0, s, b);
-      }
-    }
-    HQ_CHECK_LAUNCH();
-    // flagged rows are rare (usually none): scored inside k_pool_select, before it reads the pools
+  hipLaunchKernelGGL(k_sample_topg, dim3(sa.nqb * sa.nchunks), dim3(64), 0, s, sa);
+  HQ_CHECK_LAUNCH();
+  // (k_sample_kth clears pool_n per query: no memset)
+  const int mg = Q < 8192 ? Q : 8192;
+  launch_kth(mg, s, (const float*)sa.top, 4 * sa.nchunks, Q, sample_kth, (double)kMarginF, th0, b.pool_n, Sq32, thr0,
+             b.inv_m, qc);
+  HQ_CHECK_LAUNCH();
+  if (corpus_flags) {  // the corpus's flagged rows listed once (hq_seg_flag_rows): [count, rows...]
+    flag_n = const_cast<int*>(corpus_flags);
+    flag_list = flag_n + 1;
   } else {
-#ifdef HQ_DIAG
-    rc = f32 ? scan0_dispatch<true>(ks, b, nullptr, s) : scan0_dispatch<false>(ks, b, nullptr, s);
-#else
-    rc = launch_scan0f(b, s);
-#endif
-  }
-  if (rc) return rc;
-  if (f32) {
-    launch_pool_select(k, s, Q, b.pool_s, b.pool_i, b.pool_n, b.pool_cap, id_base, out_score, out_id,
-                       top_sample && sample_kth < k ? (const double*)th0 : (const double*)nullptr, b.thr0,
-                       qc ? &qc[0].flag : (const float*)nullptr, (int)(sizeof(QConst) / 4), b,
-                       queue_scan ? (const int*)flag_list : (const int*)nullptr,
-                       queue_scan ? (const int*)flag_n : (const int*)nullptr);
+    HQ_CHECK_HIP(hipMemsetAsync(flag_n, 0, sizeof(int), s));
+    const int64_t fb = (N + 255) / 256;
+    hipLaunchKernelGGL(k_flag_rows, dim3((unsigned)(fb < 4096 ? fb : 4096)), dim3(256), 0, s, Sc32, N, flag_list,
+                       flag_n);
     HQ_CHECK_LAUNCH();
   }
-#ifdef HQ_DIAG
-  if (b.expt == 3) {
-    unsigned long long h[7];
-    HQ_CHECK_HIP(hipMemcpyAsync(h, dbg, sizeof(h), hipMemcpyDeviceToHost, s));
-    HQ_CHECK_HIP(hipStreamSynchronize(s));
-    fprintf(stderr, "k_scan0f: waves %d, insert entries %llu, passing pairs %llu, list inserts %llu, filter passes "
-            "%llu in %llu (u, r) iterations, pre-filter fired in %llu of %llu half-steps\n", b.nqb * b.nchunks, h[0],
-            h[1], h[2], h[3], h[4], h[5], h[6]);
-  }
-  if (!f32) {
-    int mg = Q < 4096 ? Q : 4096;
-    hipLaunchKernelGGL(k_merge, dim3(mg), dim3(64), 0, s, b.ws_score, b.ws_id, (const double*)nullptr,
-                       (const int64_t*)nullptr, b.nchunks, Q, k, out_score, out_id, (double*)nullptr,
-                       (int64_t*)nullptr);
-    HQ_CHECK_LAUNCH();
-  }
-#endif
+  hipLaunchKernelGGL(k_scan0g, dim3(b.nqb * b.nchunks), dim3(64), 0, s, b);
+  HQ_CHECK_LAUNCH();
+  // flagged rows are rare (usually none): scored inside k_pool_select, before it reads the pools
+  launch_pool_select(k, s, Q, b.pool_s, b.pool_i, b.pool_n, b.pool_cap, id_base, out_score, out_id,
+                     sample_kth < k ? (const double*)th0 : (const double*)nullptr, thr0, &qc[0].flag,
+                     (int)(sizeof(QConst) / 4), b, (const int*)flag_list, (const int*)flag_n);
+  HQ_CHECK_LAUNCH();
   return HQ_OK;
 }
 
@@ -5581,8 +4243,7 @@ static int scan0_run(bool f32, int ks, const double* Zq, const double* Sq, const
 // zero-padded to 32 for the rows [0, round_up(N, 16) + kPad0), in the tiled fragment layout (z16_frag),
 // and S32 = per-row (std, mean, msq, flag bits: 1 zero variance,
 // 2 msq outside [2^-60, 2^60], 4 pad row) in SoA groups of 4 rows: group G = rows 4G .. 4G + 3 holds
-// std[4], mean[4], msq[4], flags[4] (16 floats), for the rows [0, round_up(N, 4) + kPad0).  k_scan0f
-// reads up to 31 rows past a step start.
+// std[4], mean[4], msq[4], flags[4] (16 floats), for the rows [0, round_up(N, 4) + kPad0).
 
 // one (row, value) of the split level-0 copies (row r < z16_rows(N), value c < 32)
 __device__ __forceinline__ void pack0_elem(const double* __restrict__ Z, const double* __restrict__ S, int64_t N,
@@ -5838,27 +4499,22 @@ static int refine_launch(const double* Rq, const double* Zq, const double* Sq, i
     auto kern = sm ? (raw ? k_refine_big_sm_raw : k_refine_big_sm) : (raw ? k_refine_big_raw : k_refine_big);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, VecSet{Rq, Zq, Sq}, Q, VecSet{Rc, Zc, Sc}, N, si, mode,
                        cand_score, cand_id, kp, k, threshold, thr_mode, eps, id_base, out_score, out_id, out_count,
-                       out_resolved, count_empty ? 1 : 0, out_redo, out_det, 0, next_redo, 0);
+                       out_resolved, count_empty ? 1 : 0, out_redo, out_det, next_redo, 0);
     HQ_CHECK_LAUNCH();
     return HQ_OK;
   }
   const size_t lds = ((size_t)refine_qw(si) + (size_t)kp * refine_rw(si) + (size_t)kp * (1 + si.nseg)) * 8;
-#ifdef HQ_DIAG
-  const int expt = (int)opt(OPT_REFINE_EXPT, 0);  // diagnostics build only
-#else
-  const int expt = 0;
-#endif
   if (lds <= 96 * 1024 && L % 2 == 0 && !opt_on(OPT_REFINE_GLOBAL)) {  // 16-B pieces: L even
     const void* fn = sm ? (const void*)k_refine_lds_sm : (const void*)k_refine_lds;
     HQ_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     if (sm)
       hipLaunchKernelGGL(k_refine_lds_sm, dim3(grid), dim3(256), lds, s, VecSet{Rq, Zq, Sq}, Q, VecSet{Rc, Zc, Sc},
                          N, si, mode, cand_score, cand_id, kp, k, threshold, thr_mode, eps, id_base, out_score, out_id,
-                         out_count, out_resolved, count_empty ? 1 : 0, out_redo, out_det, expt, next_redo);
+                         out_count, out_resolved, count_empty ? 1 : 0, out_redo, out_det, next_redo);
     else
       hipLaunchKernelGGL(k_refine_lds, dim3(grid), dim3(256), lds, s, VecSet{Rq, Zq, Sq}, Q, VecSet{Rc, Zc, Sc},
                          N, si, mode, cand_score, cand_id, kp, k, threshold, thr_mode, eps, id_base, out_score, out_id,
-                         out_count, out_resolved, count_empty ? 1 : 0, out_redo, out_det, expt, next_redo);
+                         out_count, out_resolved, count_empty ? 1 : 0, out_redo, out_det, next_redo);
     HQ_CHECK_LAUNCH();
     return HQ_OK;
   }
@@ -5893,7 +4549,7 @@ static int refine_launch(const double* Rq, const double* Zq, const double* Sq, i
 //   Query side: one masked copy of the block fragment per G segment (values outside the segment
 //   zeroed), so each contraction D[row][query] is that segment's G alone.
 //   Pre-filter per pair (an upper bound of the f32 model score): a G segment scores at most
-//   be + max(G, 0) ia (k_scan0f's U(G) with sqrt(A^2 G^2 + B^2) <= A |G| + |B|: be = 0.35 + |B| /
+//   be + max(G, 0) ia (gstar0's U(G) with sqrt(A^2 G^2 + B^2) <= A |G| + |B|: be = 0.35 + |B| /
 //   (2 sqrt Q), ia = c1 + A / (2 sqrt Q); a zero-variance candidate scores 0.1 <= be; a zero-variance
 //   query segment is bounded by be = 1, ia = 0), a one-value segment 1 when the two values are within
 //   1e-6 plus f32 slack, else 0.  Pairs whose weighted bound reaches the query's threshold are queued
@@ -6279,12 +4935,12 @@ __device__ __forceinline__ void ov_bound(const flt4* acc, const float* wia, floa
 }
 
 // One wave = 32 queries (two blocks b of 16; lane (g, j) owns queries 16b + j) x one chunk, 16 rows per
-// step (lane group g owns rows 4g + r: the MFMA D layout), NG MFMAs (HI: hi.hi only) or NG x 3 (split) per
-// block and step.  HI: the bound takes G_hihi, each segment's slack |G_split - G_hihi| < 1e-3 m + 1e-4 (as
+// step (lane group g owns rows 4g + r: the MFMA D layout), NG MFMAs (hi.hi only) per block and step at 4
+// waves per SIMD.  The bound takes G_hihi, each segment's slack |G_split - G_hihi| < 1e-3 m + 1e-4 (as
 // k_scan0g) folded into bsum (relu(G + d) <= relu(G) + d), and the drain recomputes the split G of every
-// queued pair (ov_split_g) for the model score; the queue then holds the (row, query) key only.
+// queued pair (ov_split_g) for the model score; the queue holds the (row, query) key only.
 //
-// LIN (default with HI): the weighted relu sum in two parts, w relu(G) = s (G + |G|) with s = w ia / 2
+// LIN (default; lists up to 64): the weighted relu sum in two parts, w relu(G) = s (G + |G|) with s = w ia / 2
 // per segment and query.  The query's masked copies are pre-scaled by s in f16 (acc_i = s_i G_i), one
 // more contraction of the shared K-block with per-segment scaled values (seeded with K-block 0's
 // acc_0 when that block holds segment 0 alone) gives the linear part sum_i s_i G_i, and the bound is
@@ -6294,12 +4950,12 @@ __device__ __forceinline__ void ov_bound(const flt4* acc, const float* wia, floa
 // a drain gate on the model at G_hihi + slack before the split measured slower, 0.69M, as did keeping
 // G_hihi in the queue: the kernel is not bound by the drain's split recompute).  The f16 scaling errs by <= 2^-11 s_i sum|q c| <= 2^-11 s_i m_i
 // in each part (Cauchy-Schwarz on unit-variance vectors), folded into bsum with the hi.hi slack.
-template <int LID, int OCC, bool HI = true, bool LIN = HI, int PF = 1>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OCC))) void k_scanov(OvArgs a) {
+// LIN = false (longer lists): the med3 + fma bound (ov_bound) with pool appends straight to global memory.
+template <int LID, bool LIN = true>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void k_scanov(OvArgs a) {
   using T = OvT<LID>;
   constexpr int NG = T::NG, NC = T::NC, NKB = T::NKB, NB = kOvQW / 16, GS = 16 * NG + 4 * NC + 8;
-  __shared__ flt4 qg[HI ? 1 : kOvQCap];  // queue: G of each G segment (split form) ...
-  __shared__ int qk[kOvQCap];   // ... and (row - c_begin) << 5 | query within the wave
+  __shared__ int qk[kOvQCap];   // queue: (row - c_begin) << 5 | query within the wave
   __shared__ QOvD qs[kOvQW];    // the wave's model constants (the drain reads them per entry)
   // LIN: pool appends collected in LDS and written after the scan loop, so the loop issues no global
   // store or atomic: on gfx9 the vector-memory counter is not ordered between loads and stores, and a
@@ -6335,8 +4991,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OCC))) void 
   }
   wave_lds_sync();
 
-  static_assert(!LIN || HI, "the LIN bound is a hi.hi form");
-  half8 qh[NB][NG], ql[HI ? 1 : NB][NG], qlin[LIN ? NB : 1];
+  half8 qh[NB][NG], qlin[LIN ? NB : 1];
   float wia[LIN ? 1 : NB][NG], bsum[NB], wt[NB], qv[NB][NC > 0 ? NC : 1], tolq[NB][NC > 0 ? NC : 1];
 #pragma unroll
   for (int b = 0; b < NB; ++b) {
@@ -6344,7 +4999,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OCC))) void 
     const bool v = q < a.Q;
     const int qq = v ? q : 0;
     half8 lo_unused[NG];
-    ov_query_frags<T>(a, qq, g, qh[b], HI ? lo_unused : ql[HI ? 0 : b]);
+    ov_query_frags<T>(a, qq, g, qh[b], lo_unused);
     const QOv& c = a.qc[qq];
     float wi[NG];
 #pragma unroll
@@ -6354,10 +5009,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OCC))) void 
       for (int i = 0; i < NG; ++i) wia[b][i] = wi[i];
     }
     bsum[b] = c.bsum;
-    if constexpr (HI) {
 #pragma unroll
-      for (int i = 0; i < NG; ++i) bsum[b] = fmaf(wi[i], 1e-3f * (float)o.gplen[i] + 1e-4f, bsum[b]);
-    }
+    for (int i = 0; i < NG; ++i) bsum[b] = fmaf(wi[i], 1e-3f * (float)o.gplen[i] + 1e-4f, bsum[b]);
 #pragma unroll
     for (int ci = 0; ci < NC; ++ci) { qv[b][ci] = c.cv[ci]; tolq[b][ci] = c.tolq[ci]; }
     wt[b] = (v && __float_as_int(c.flag) == 0) ? c.wthr : __builtin_huge_valf();  // flagged query: dense path
@@ -6392,7 +5045,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OCC))) void 
   const _Float16* zb = a.Zc + (c_begin >> 4) * NKB * kZ16Tile + lane * 8;
   const float* sb = a.Sc32 + (c_begin >> 2) * GS;  // one-value segment values of the step's first group
   struct CStep {
-    half8 f[NKB][HI ? 1 : 2];
+    half8 f[NKB];  // hi fragments
     flt4 cv[NC > 0 ? NC : 1];
     flt4 ro;
   };
@@ -6401,10 +5054,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OCC))) void 
     s = s < nsteps ? s : nsteps - 1;  // the prefetch stays inside the chunk
     const _Float16* p = zb + s * (NKB * kZ16Tile);
 #pragma unroll
-    for (int kb = 0; kb < NKB; ++kb) {
-      c.f[kb][0] = *reinterpret_cast<const half8*>(p + kb * kZ16Tile);
-      if constexpr (!HI) c.f[kb][HI ? 0 : 1] = *reinterpret_cast<const half8*>(p + kb * kZ16Tile + kZ16Lo);
-    }
+    for (int kb = 0; kb < NKB; ++kb) c.f[kb] = *reinterpret_cast<const half8*>(p + kb * kZ16Tile);
     const float* sp = sb + (s * 4 + g) * GS;
 #pragma unroll
     for (int ci = 0; ci < NC; ++ci) c.cv[ci] = *reinterpret_cast<const flt4*>(sp + 4 * ci);
@@ -6424,13 +5074,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OCC))) void 
       const QOvD& c = qs[eqi];
       if (row < c_end) {
         float G[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        if constexpr (HI) {
-          ov_split_g<T>(a.Zq, a.Zc, q, row, G);
-        } else {
-          const flt4 eg = qg[lane];
-#pragma unroll
-          for (int i = 0; i < 4; ++i) G[i] = eg[i];
-        }
+        ov_split_g<T>(a.Zq, a.Zc, q, row, G);
         const float s = ov_model<NG, NC>(o, c, a.Sc32, row, G, a.Sq, a.Sc, q);
         if constexpr (LIN) {
           ok = s >= c.thl;
@@ -6462,17 +5106,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OCC))) void 
     wave_lds_sync();
     for (int b0 = n; b0 < qn; b0 += 64) {
       const bool mv = b0 + lane < qn;
-      flt4 tg = {0.0f, 0.0f, 0.0f, 0.0f};
       int tk = 0;
-      if (mv) {
-        if constexpr (!HI) tg = qg[b0 + lane];
-        tk = qk[b0 + lane];
-      }
+      if (mv) tk = qk[b0 + lane];
       wave_lds_sync();
-      if (mv) {
-        if constexpr (!HI) qg[b0 - n + lane] = tg;
-        qk[b0 - n + lane] = tk;
-      }
+      if (mv) qk[b0 - n + lane] = tk;
       wave_lds_sync();
     }
     qn -= n;
@@ -6482,18 +5119,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OCC))) void 
     flt4 acc[NG];
 #pragma unroll
     for (int i = 0; i < NG; ++i)
-      acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(cur.f[T::kb(i)][0], qh[b][i], flt4{0, 0, 0, 0}, 0, 0, 0);
-    if constexpr (!HI) {
-#pragma unroll
-      for (int i = 0; i < NG; ++i)
-        acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(cur.f[T::kb(i)][0], ql[HI ? 0 : b][i], acc[i], 0, 0, 0);
-#pragma unroll
-      for (int i = 0; i < NG; ++i)
-        acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(cur.f[T::kb(i)][HI ? 0 : 1], qh[b][i], acc[i], 0, 0, 0);
-    }
+      acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(cur.f[T::kb(i)], qh[b][i], flt4{0, 0, 0, 0}, 0, 0, 0);
     float U[4], W[4];
     if constexpr (LIN) {
-      const flt4 al = __builtin_amdgcn_mfma_f32_16x16x32_f16(cur.f[T::LKB][0], qlin[b], T::LC0 ? acc[0] : flt4{0, 0, 0, 0},
+      const flt4 al = __builtin_amdgcn_mfma_f32_16x16x32_f16(cur.f[T::LKB], qlin[b], T::LC0 ? acc[0] : flt4{0, 0, 0, 0},
                                                               0, 0, 0);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -6520,12 +5149,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OCC))) void 
       if (m) {
         if ((m >> lane) & 1ull) {
           const int pos = qn + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-          if constexpr (!HI) {
-            flt4 gg = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-            for (int i = 0; i < NG; ++i) gg[i] = acc[i][r];
-            qg[pos] = gg;
-          }
           qk[pos] = (int)((cs - c_begin + 4 * g + r) << 5) | (16 * b + j);
         }
         qn += __popcll(m);
@@ -6558,42 +5181,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OCC))) void 
       if (lane < 32 && ((over >> lane) & 1u) && q0 + lane < a.Q) atomicAdd(a.pool_n + q0 + lane, a.pool_cap + 1);
     }
   };
-  if constexpr (PF == 1) {  // two buffers, ping-pong
-    CStep cA, cB;
-    load_step(cA, 0);
-    int64_t s = 0;
-    for (; s + 1 < nsteps; s += 2) {
-      load_step(cB, s + 1);
-      __builtin_amdgcn_sched_barrier(0);
-      step(cA, s);
-      load_step(cA, s + 2);
-      __builtin_amdgcn_sched_barrier(0);
-      step(cB, s + 1);
-    }
-    if (s < nsteps) step(cA, s);
-    wave_lds_sync();
-    while (qn > 0) drain(qn < 64 ? qn : 64);
-    flush();
-    return;
-  }
-  // PF + 1 step buffers in rotation: step s + PF is requested while step s is scored (load_step clamps
-  // the index to the chunk's last step)
-  CStep buf[PF + 1];
-#pragma unroll
-  for (int u = 0; u < PF; ++u) load_step(buf[u], u);
-  auto body = [&](const int64_t st, const CStep& cur, CStep& nn) {
-    load_step(nn, st + PF);
-    __builtin_amdgcn_sched_barrier(0);  // keep the prefetch PF steps ahead
-    step(cur, st);
-  };
+  // two step buffers, ping-pong: step s + 1 is requested while step s is scored
+  CStep cA, cB;
+  load_step(cA, 0);
   int64_t s = 0;
-  for (; s + PF < nsteps; s += PF + 1) {
-#pragma unroll
-    for (int u = 0; u <= PF; ++u) body(s + u, buf[u], buf[(u + PF) % (PF + 1)]);
+  for (; s + 1 < nsteps; s += 2) {
+    load_step(cB, s + 1);
+    __builtin_amdgcn_sched_barrier(0);
+    step(cA, s);
+    load_step(cA, s + 2);
+    __builtin_amdgcn_sched_barrier(0);
+    step(cB, s + 1);
   }
-#pragma unroll
-  for (int u = 0; u < PF; ++u)
-    if (s + u < nsteps) step(buf[u], s + u);
+  if (s < nsteps) step(cA, s);
   wave_lds_sync();
   while (qn > 0) drain(qn < 64 ? qn : 64);
   flush();
@@ -6601,10 +5201,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OCC))) void 
 
 // Sample pass of the overall scan (as k_sample_topg): 16 queries per wave, whole sample tiles; per lane
 // the step whose four rows hold the largest pre-filter bound is kept and its rows are scored with the
-// model in the epilogue; the stream's kTopT best go to the pool for k_sample_kth.  HI (default): the step
-// loop contracts hi.hi only (the kept step is a heuristic choice: any choice leaves the sample's scores real
-// scores of distinct pairs) and the epilogue recomputes the kept rows' split G (ov_split_g) for the model.
-template <int LID, bool HI = true>
+// model in the epilogue; the stream's kTopT best go to the pool for k_sample_kth.  The step loop contracts
+// the split G (three MFMAs per segment), so the epilogue scores the kept accumulators as they are.
+template <int LID>
 __global__ __launch_bounds__(64) void k_sampleov(OvArgs a) {
   using T = OvT<LID>;
   constexpr int NG = T::NG, NC = T::NC, NKB = T::NKB, GS = 16 * NG + 4 * NC + 8;
@@ -6630,7 +5229,7 @@ __global__ __launch_bounds__(64) void k_sampleov(OvArgs a) {
 #pragma unroll
     for (int kb = 0; kb < NKB; ++kb) {
       f[kb][0] = *reinterpret_cast<const half8*>(p + kb * kZ16Tile);
-      if constexpr (!HI) f[kb][1] = *reinterpret_cast<const half8*>(p + kb * kZ16Tile + kZ16Lo);
+      f[kb][1] = *reinterpret_cast<const half8*>(p + kb * kZ16Tile + kZ16Lo);
     }
     const int64_t r0 = row_of(cs + 4 * g);
     const float* sp = a.Sc32 + (r0 >> 2) * GS;
@@ -6651,12 +5250,10 @@ __global__ __launch_bounds__(64) void k_sampleov(OvArgs a) {
     flt4 acc[NG];
 #pragma unroll
     for (int i = 0; i < NG; ++i) acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(f0[T::kb(i)][0], qh[i], flt4{0, 0, 0, 0}, 0, 0, 0);
-    if constexpr (!HI) {
 #pragma unroll
-      for (int i = 0; i < NG; ++i) acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(f0[T::kb(i)][0], ql[i], acc[i], 0, 0, 0);
+    for (int i = 0; i < NG; ++i) acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(f0[T::kb(i)][0], ql[i], acc[i], 0, 0, 0);
 #pragma unroll
-      for (int i = 0; i < NG; ++i) acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(f0[T::kb(i)][1], qh[i], acc[i], 0, 0, 0);
-    }
+    for (int i = 0; i < NG; ++i) acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(f0[T::kb(i)][1], qh[i], acc[i], 0, 0, 0);
     float U[4];
     ov_bound<T>(acc, c.wia, c.bsum, o, c.cv, c.tolq, v0, ro0, U);
     float m = -__builtin_huge_valf();
@@ -6671,7 +5268,7 @@ __global__ __launch_bounds__(64) void k_sampleov(OvArgs a) {
 #pragma unroll
     for (int kb = 0; kb < NKB; ++kb) {
       f0[kb][0] = f1[kb][0];
-      if constexpr (!HI) f0[kb][1] = f1[kb][1];
+      f0[kb][1] = f1[kb][1];
     }
 #pragma unroll
     for (int ci = 0; ci < NC; ++ci) v0[ci] = v1[ci];
@@ -6687,12 +5284,8 @@ __global__ __launch_bounds__(64) void k_sampleov(OvArgs a) {
       const int64_t i = (int64_t)bcs + 4 * g + r;
       if (i >= c_end) continue;
       float G[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-      if constexpr (HI) {
-        ov_split_g<T>(a.Zq, a.Zc, q, row_of(i), G);
-      } else {
 #pragma unroll
-        for (int s = 0; s < NG; ++s) G[s] = bg[s][r];
-      }
+      for (int s = 0; s < NG; ++s) G[s] = bg[s][r];
       float sc = ov_model<NG, NC>(o, c, a.Sc32, row_of(i), G, a.Sq, a.Sc, q);
       if (sc < 0.0f) continue;
 #pragma unroll
@@ -6776,17 +5369,14 @@ struct OvPlan {
 
 static OvPlan ov_plan(int Q, int64_t N, int k) {
   OvPlan p;
-  // one round of waves at the kernel's occupancy (the hi.hi form: 4 waves per SIMD, 128 VGPRs; option
-  // ov_occ 2 / 3)
-  const int occ = (int)opt(OPT_OV_OCC, 4) == 2 ? 2 : ((int)opt(OPT_OV_OCC, 4) == 3 ? 3 : 4);
-  int w = opt(OPT_OV_WAVES, 0) > 0 ? (int)opt(OPT_OV_WAVES, 0) : 1024 * occ;
+  // one round of waves at the kernel's occupancy (4 waves per SIMD, 128 VGPRs)
+  int w = 4096;
   ov_geometry(Q, N, kOvQW, w, 1 << 20, p.nqb, p.nchunks, p.chunk_len);
   while (p.chunk_len > (int64_t(1) << 26)) {  // queue keys hold (row - chunk start) << 5
     w *= 2;
     ov_geometry(Q, N, kOvQW, w, 1 << 20, p.nqb, p.nchunks, p.chunk_len);
   }
-  const int64_t sd = opt(OPT_SAMPLE_STRIDE, 16) > 0 ? opt(OPT_SAMPLE_STRIDE, 16) : 16;
-  p.stride = N >= sd * 4096 ? sd : (N / 4096 > 1 ? N / 4096 : 1);
+  p.stride = sampling_stride(N);
   p.S = sample_rows_tiled(N, p.stride);
   ov_geometry(Q, p.S, 16, 4096, 64 * kKthReg / (4 * kTopT), p.s_nqb, p.s_nchunks, p.s_chunk_len);
   p.pool_cap = pool_cap_for(p.nchunks, k, N, p.stride, scan_kprime(k, p.stride));
@@ -6833,13 +5423,12 @@ static int ov_launch(const OvArgs& a0, const OvPlan& p, const SegInfo& si, int k
   sa.nchunks = p.s_nchunks;
   sa.chunk_len = p.s_chunk_len;
   sa.top = reinterpret_cast<float*>(ws + p.off_top);
-  // the split sample by default: the hi.hi form's epilogue (split G of the kept rows) measured 139 vs 106 us
-  if (opt(OPT_SAMPLE_HI, 0) == 1) hipLaunchKernelGGL((k_sampleov<LID, true>), dim3(sa.nqb * sa.nchunks), dim3(64), 0, s, sa);
-  else hipLaunchKernelGGL((k_sampleov<LID, false>), dim3(sa.nqb * sa.nchunks), dim3(64), 0, s, sa);
+  // (a hi.hi step loop with the split G of the kept rows recomputed in the epilogue measured 139 vs 106 us)
+  hipLaunchKernelGGL(k_sampleov<LID>, dim3(sa.nqb * sa.nchunks), dim3(64), 0, s, sa);
   HQ_CHECK_LAUNCH();
   const int mg = Q < 8192 ? Q : 8192;
   launch_kth(mg, s, (const float*)sa.top, 4 * sa.nchunks, Q, sample_kth, (double)kMarginF, th0,
-             (unsigned long long*)nullptr, a.pool_n, (const float*)nullptr, thr0, 0.0, (QConst*)nullptr);
+             a.pool_n, (const float*)nullptr, thr0, 0.0, (QConst*)nullptr);
   HQ_CHECK_LAUNCH();
   hipLaunchKernelGGL(k_ov_qconst, dim3((Q + 255) / 256), dim3(256), 0, s, a.Sq32, Q, a.o, (const double*)th0, thr0, qc);
   HQ_CHECK_LAUNCH();
@@ -6850,31 +5439,16 @@ static int ov_launch(const OvArgs& a0, const OvPlan& p, const SegInfo& si, int k
   hipLaunchKernelGGL(k_ov_flag_rows, dim3((unsigned)(fb < 4096 ? fb : 4096)), dim3(256), 0, s, a.Sc32, a.N, GS,
                      4 * a.o.nc, flag_list, flag_n);
   HQ_CHECK_LAUNCH();
-  // default: the hi.hi form at 4 waves per SIMD (option ov_occ 2 / 3); option scanov_split3: the split form
-  const int oocc = (int)opt(OPT_OV_OCC, 4);
-  if (opt_on(OPT_SCANOV_SPLIT3)) {
-    if (oocc == 3) hipLaunchKernelGGL((k_scanov<LID, 3, false>), dim3(a.nqb * a.nchunks), dim3(64), 0, s, a);
-    else hipLaunchKernelGGL((k_scanov<LID, 2, false>), dim3(a.nqb * a.nchunks), dim3(64), 0, s, a);
-  } else if (opt_on(OPT_SCANOV_V1) || k > kMaxTopK) {
+  if (k > kMaxTopK) {
     // the med3 + fma bound with pool appends straight to global memory: long lists (k > 64) pass more pairs
     // per wave than the LIN form's 256-entry LDS append buffer holds (its overflow sends queries to the
     // dense path)
-    hipLaunchKernelGGL((k_scanov<LID, 4, true, false>), dim3(a.nqb * a.nchunks), dim3(64), 0, s, a);
-  } else if (opt(OPT_OV_PF, 1) == 2) {  // prefetch distance (steps)
-    if (oocc == 3) hipLaunchKernelGGL((k_scanov<LID, 3, true, true, 2>), dim3(a.nqb * a.nchunks), dim3(64), 0, s, a);
-    else hipLaunchKernelGGL((k_scanov<LID, 4, true, true, 2>), dim3(a.nqb * a.nchunks), dim3(64), 0, s, a);
-  } else if (opt(OPT_OV_PF, 1) == 3) {
-    if (oocc == 3) hipLaunchKernelGGL((k_scanov<LID, 3, true, true, 3>), dim3(a.nqb * a.nchunks), dim3(64), 0, s, a);
-    else hipLaunchKernelGGL((k_scanov<LID, 4, true, true, 3>), dim3(a.nqb * a.nchunks), dim3(64), 0, s, a);
-  } else if (oocc == 2) {
-    hipLaunchKernelGGL((k_scanov<LID, 2>), dim3(a.nqb * a.nchunks), dim3(64), 0, s, a);
-  } else if (oocc == 3) {
-    hipLaunchKernelGGL((k_scanov<LID, 3>), dim3(a.nqb * a.nchunks), dim3(64), 0, s, a);
+    hipLaunchKernelGGL((k_scanov<LID, false>), dim3(a.nqb * a.nchunks), dim3(64), 0, s, a);
   } else {
     // (round 6: one ballot over a block's four rows before the per-row queueing — the rows' bound chains
     // independent — spilled at 4 waves per SIMD (873 -> 2420 us per 1000 x 1M scan) and measured 16% slower
     // at 3 (0.77 vs 0.91M QPS, no spill): profiles/r06_ab_rank_ct.txt, r06_ab_final_select.txt; not kept)
-    hipLaunchKernelGGL((k_scanov<LID, 4>), dim3(a.nqb * a.nchunks), dim3(64), 0, s, a);
+    hipLaunchKernelGGL((k_scanov<LID, true>), dim3(a.nqb * a.nchunks), dim3(64), 0, s, a);
   }
   HQ_CHECK_LAUNCH();
   hipLaunchKernelGGL(k_scanov_flagged, dim3(64, (Q + 63) / 64), dim3(64), 0, s, a, si, (const int*)flag_list,
@@ -6911,7 +5485,7 @@ int hq_scan0_geometry(int Q, int64_t N, int* nqb, int* nchunks, int64_t* chunk_l
   if (Q <= 0 || N <= 0) return fail(HQ_E_INVALID, "bad shape Q=%d N=%lld", Q, (long long)N);
   int a = 0, b = 0;
   int64_t c = 0;
-  scan0_geometry(Q, N, a, b, c, kQW, opt(OPT_SCAN_OCC, 3) == 3 ? 3 : 4);  // the default scan's geometry
+  scan0_geometry(Q, N, a, b, c);
   if (nqb) *nqb = a;
   if (nchunks) *nchunks = b;
   if (chunk_len) *chunk_len = c;
@@ -6950,7 +5524,7 @@ int hq_seg_prepare_rows(const double* idx, int64_t N, int L, int src_f32, const 
   seg_info(L, si);
   if (si.nseg == 0) return fail(HQ_E_INVALID, "no level structure for L=%d", L);
   const int64_t total = N * si.nseg;
-  if (N <= 16384 && si.L <= 4096 && !opt_on(OPT_SEG_PREPARE_FLAT)) {  // A/B option: the flat kernel
+  if (N <= 16384 && si.L <= 4096) {
     hipLaunchKernelGGL(k_seg_prepare_lds, dim3((unsigned)N), dim3(64), (size_t)8 * si.L, (hipStream_t)stream, idx, N,
                        si, src_f32 ? 1 : 0, row_f32, Z, stats);
   } else {
@@ -7093,7 +5667,7 @@ int hq_refine_final_ws(const double* Rq, const double* Zq, const double* Sq, int
       (N > 0 && (!Rc || !Zc || !Sc)))
     return fail(HQ_E_INVALID, "null buffer");
   if (big && workspace_bytes < hq_refine_workspace_size(Q, kp, L)) return fail(HQ_E_INVALID, "workspace too small");
-  const FinalOut fin{K_out, fin_id, fin_det, fin_count, opt(OPT_FINAL_ROUNDS, 1) != 0 ? 1 : 0};
+  const FinalOut fin{K_out, fin_id, fin_det, fin_count, 1};
   // records on (the final ranking reads them from the workspace), count_empty on (nothing passed: redo)
   double* dummy_det = fin_det;
   return refine_launch(Rq, Zq, Sq, Q, Rc, Zc, Sc, N, L, 0, cand_score, cand_id, kp, k, threshold, thr_mode, eps,
@@ -7128,17 +5702,6 @@ int hq_scan_topk(const double* Zq, const double* Sq, int Q, const double* Zc, co
   }
   if (!Zq || !Sq || !Zc || !Sc || !workspace) return fail(HQ_E_INVALID, "null buffer");
   if (workspace_bytes < hq_scan_workspace_size(Q, N, k)) return fail(HQ_E_INVALID, "workspace too small");
-#ifdef HQ_DIAG
-  // diagnostics builds: the f64 wave-level level-0 scan (option scan_variant = 64)
-  if (mode == 0 && !out_best && !out_best_id && N < 0x7FFFFFFF && opt(OPT_SCAN_VARIANT, 0) == 64) {
-    SegInfo si;
-    seg_info(L, si);
-    const int ks = si.plen[0] / 4;
-    if (ks >= 1 && ks <= 8)
-      return scan0_run(false, ks, Zq, Sq, nullptr, nullptr, Q, Zc, Sc, nullptr, nullptr, N, si, k, threshold,
-                       thr_mode, id_base, workspace, out_score, out_id, s);
-  }
-#endif
   ScanArgs a;
   a.Zq = Zq; a.Sq = Sq; a.Q = Q; a.Zc = Zc; a.Sc = Sc; a.N = N;
   seg_info(L, a.si);
@@ -7265,9 +5828,8 @@ int hq_scan0_topk_split_fl(const void* Zq16, const float* Sq32, const double* Sq
   seg_info(L, si);
   const int ks = si.nseg > 0 ? si.plen[0] / 4 : 0;
   if (ks < 1 || ks > 8) return fail(HQ_E_UNSUPPORTED, "level-0 segment of %d values (1..32)", si.plen[0]);
-  return scan0_run(true, ks, nullptr, Sq, reinterpret_cast<const _Float16*>(Zq16), Sq32, Q, nullptr, Sc,
-                   reinterpret_cast<const _Float16*>(Zc16), Sc32, N, si, k, threshold, thr_mode, id_base, workspace,
-                   out_score, out_id, s, corpus_flags);
+  return scan0_run(Sq, reinterpret_cast<const _Float16*>(Zq16), Sq32, Q, Sc, reinterpret_cast<const _Float16*>(Zc16),
+                   Sc32, N, si, k, threshold, thr_mode, id_base, workspace, out_score, out_id, s, corpus_flags);
 }
 
 int hq_rescore(const double* Rq, const double* Zq, const double* Sq, int Q, const double* Rc, const double* Zc,
@@ -7322,7 +5884,7 @@ int hq_progressive_final_ex(int R, int Q, int M, int nseg, const double* s0, con
   else
     hipLaunchKernelGGL(k_progressive_final_big, dim3(grid), dim3(256), 0, (hipStream_t)stream, R, Q, M, W, s0, ids,
                        det, best, best_id, best_det, K, out_id, out_det, out_count,
-                       (flags & 1) | (opt(OPT_FINAL_ROUNDS, 1) != 0 ? 0 : 2));  // option final_rounds = 0: sort only
+                       flags & 1);
   HQ_CHECK_LAUNCH();
   return HQ_OK;
 }

@@ -273,6 +273,21 @@ class Prepared:
         return (self.S[:, :, 3] >= 2.0).any(dim=1)
 
 
+def _row_flags(src_f32: bool, row_f32, n: int, dev, all_needs_rows: bool = True):
+    """(rf, any32, all32) of a batch of n rows: the device uint8 flag per row for the library (None when
+    src_f32 covers every row or no flags were given), and whether any / every row is a float32 index vector.
+    all_needs_rows: per-row flags of an empty batch do not make it all-float32 (seg_append passes False: its
+    empty batch changes nothing)."""
+    any32 = all32 = bool(src_f32)
+    if row_f32 is None or src_f32:
+        return None, any32, all32
+    flags = np.asarray(row_f32, dtype=bool).reshape(-1)
+    if flags.size != n:
+        raise ValueError("row_f32 needs one flag per row")
+    any32, all32 = bool(flags.any()), bool(flags.all()) and (n > 0 or not all_needs_rows)
+    return _contig(torch().from_numpy(flags.astype(np.uint8)).to(dev)), any32, all32
+
+
 def seg_prepare(idx, exc=None, src_f32: bool = False, row_f32=None) -> Prepared:
     """src_f32: every row is a float32 index vector; row_f32 (bool per row, host or device): some are
     (hq_seg_prepare_rows).  The reference computes those rows' statistics and scores in float32."""
@@ -282,14 +297,7 @@ def seg_prepare(idx, exc=None, src_f32: bool = False, row_f32=None) -> Prepared:
     Lp, ns = seg_padded_len(L), seg_count(L)
     Z = t.empty((N, Lp), dtype=t.float64, device=i2.device)
     S = t.empty((N, ns, 4), dtype=t.float64, device=i2.device)
-    rf = None
-    any32 = all32 = bool(src_f32)
-    if row_f32 is not None and not src_f32:
-        flags = np.asarray(row_f32, dtype=bool).reshape(-1)
-        if flags.size != N:
-            raise ValueError("row_f32 needs one flag per row")
-        any32, all32 = bool(flags.any()), bool(flags.all()) and N > 0
-        rf = _contig(t.from_numpy(flags.astype(np.uint8)).to(i2.device))
+    rf, any32, all32 = _row_flags(src_f32, row_f32, N, i2.device)
     if N:
         _chk(_L().hq_seg_prepare_rows(ptr(i2), N, L, 1 if src_f32 else 0, ptr(rf), ptr(Z), ptr(S), stream()), exc)
     return Prepared(i2, Z, S, L, any32, all32)
@@ -346,14 +354,7 @@ def seg_prepare_pack0(idx, exc=None, src_f32: bool = False, row_f32=None) -> Pre
     Lp, ns = seg_padded_len(L), seg_count(L)
     Z = t.empty((N, Lp), dtype=t.float64, device=i2.device)
     S = t.empty((N, ns, 4), dtype=t.float64, device=i2.device)
-    rf = None
-    any32 = all32 = bool(src_f32)
-    if row_f32 is not None and not src_f32:
-        flags = np.asarray(row_f32, dtype=bool).reshape(-1)
-        if flags.size != N:
-            raise ValueError("row_f32 needs one flag per row")
-        any32, all32 = bool(flags.any()), bool(flags.all()) and N > 0
-        rf = _contig(t.from_numpy(flags.astype(np.uint8)).to(i2.device))
+    rf, any32, all32 = _row_flags(src_f32, row_f32, N, i2.device)
     p = Prepared(i2, Z, S, L, any32, all32)
     p.Z16 = t.empty(((N + 15) // 16 * 16 + PAD0, 64), dtype=t.float16, device=i2.device)
     p.S32 = t.empty(((N + 3) // 4 * 4 + PAD0, 4), dtype=t.float32, device=i2.device)
@@ -426,14 +427,7 @@ def seg_append(p: Prepared, rows, src_f32: bool = False, row_f32=None, exc=None)
     M, L = r2.shape
     if L != p.L:
         raise ValueError(f"appended index length {L} != corpus index length {p.L}")
-    rf = None
-    any32 = all32 = bool(src_f32)
-    if row_f32 is not None and not src_f32:
-        flags = np.asarray(row_f32, dtype=bool).reshape(-1)
-        if flags.size != M:
-            raise ValueError("row_f32 needs one flag per row")
-        any32, all32 = bool(flags.any()), bool(flags.all())
-        rf = _contig(t.from_numpy(flags.astype(np.uint8)).to(r2.device))
+    rf, any32, all32 = _row_flags(src_f32, row_f32, M, r2.device, all_needs_rows=False)
     if M == 0:
         return p
     N0, N1 = p.N, p.N + M
@@ -486,7 +480,7 @@ def scan_topk(q: Prepared, c: Prepared, mode: int, k: int, threshold: float = 0.
     """Fused MFMA scan + per-query top-k on APPROXIMATE scores.  mode 0: level-0 score, 1: overall.
     thr_mode 0 none / 1 >= / 2 >.  Returns (scores [Q, k], ids [Q, k], best [Q], best_id [Q]); best and
     best_id (first arg-max of the approximate score) are None unless need_best (the level-0 scan without
-    the arg-max runs the wave-independent k_scan0 kernel)."""
+    the arg-max runs the split-f16 queue scan: k_sample_topg, k_scan0g, k_pool_select)."""
     t = torch()
     Q, N = q.N, c.N
     dev = q.Z.device

@@ -54,13 +54,7 @@ const char* hq_last_error(void);
  * e.g. "fused_v" (fused-kernel variant bits), "fused_generic", "chunk_generic", "chunk_exactdiv",
  * "chunk_wpb", "chunk_cpw", "precomp_grid", "precomp_tree_lds", "cos_kernel" (1 register-staged,
  * 2 lockstep), "refine_global", "select_2stage", "level_scores_v1" (the one-thread-per-pair dense scorer),
- * "scan_split3" (the level-0 scan's pre-filter on the three-MFMA split contraction instead of hi.hi),
- * "scan_occ" (3 (default) / 4 / 5 / 6: the level-0 scan's register target in waves per SIMD), "scanov_split3" (the
- * overall scan's pre-filter on the split contraction), "ov_occ" (2 / 3 / 4: the overall scan's target),
- * "sample_hi" (1: the sample passes' step loops on hi.hi with a split-G epilogue),
- * "sample_kth" (0 = provable bound), "scan_v1" (the
- * LDS-tiled level-0 scan), "scan_variant", "scan_wpb" (4 = four waves per level-0 scan block), "scan_pf" (prefetch
- * distance 2, 3, 4, 6 or 8; default 6 at scan_occ 3, else 4), "sample_variant" (1 = the full-filter sample pass),
+ * "sample_kth" (0 = provable bound), "scan_v1" (the LDS-tiled f64 scans instead of the split-f16 ones),
  * "rank_ct" (0: the long-list re-rank's runtime level structure; 2: the compile-time one in the short-list kernel too),
  * "rank_win" (0: the long-list ranking by the bitonic sort alone, no window ranking), "rank_sort_nt" (512: lists
  * > 512 in 512-thread workgroups), "rank_sort_small" (0: lists <= 128 in the 1024-entry workgroup).  Options are
@@ -73,11 +67,11 @@ int hq_set_option(const char* name, int64_t value);
 int hq_reset_option(const char* name);
 int hq_get_option(const char* name, int64_t* value);
 int hq_diag_build(void);
-/* DIAG builds: bounds violations counted by the guarded corpus-row loads of the level-0 scan (k_scan0f,
- * k_sample_topf, k_pool_select; the load is clamped instead of faulting) since the library loaded, and
+/* DIAG builds: bounds violations counted by the guarded corpus-row loads of the level-0 scan (k_scan0g,
+ * k_sample_topg, k_pool_select; the load is clamped instead of faulting) since the library loaded, and
  * the source line of the first.  Synchronises the device.  Default builds report 0.                  */
 int hq_diag_violations(int64_t* count, int* first_line);
-/* Launch geometry of the level-0 scan k_scan0f (host only): query blocks of 64, corpus chunks (a multiple
+/* Launch geometry of the level-0 scan k_scan0g, exactly as launched (host only): query blocks of 64, corpus chunks (a multiple
  * of 8: XCD map) of chunk_len rows (a multiple of 16), and the row counts of the split copies it reads
  * (Z16: z_rows = round_up(N, 16) + 48 rows of 64 halves in the tiled fragment layout, S32: s_rows =
  * round_up(N, 4) + 48).  A C caller of hq_seg_pack0_split allocates z_rows x 64 halves and s_rows x 4

@@ -247,10 +247,9 @@ def test_rag_scores(hq_lib, golden):
 
 
 def test_level0_scan_kernels_agree_and_match_oracle(hq_lib, hq_option):
-    """The level-0 scan variants (k_scan0g at 1 or 4 waves per block, 64 or 128 queries per wave, 4 or 3 waves per SIMD and prefetch distance 2-8, the
-    G-selected or full-filter sample pass or none, the list-based k_scan0f) give the same exact top-k as
-    the LDS-tiled k_scan (option scan_v1) and as the oracle, on a corpus with a ragged chunk tail, zero-variance level-0 segments on both sides,
-    duplicate runs across chunks and a query count that is not a multiple of 64."""
+    """The level-0 scan (k_sample_topg + k_scan0g + k_pool_select) gives the same exact top-k as the LDS-tiled
+    k_scan (option scan_v1) and as the oracle, on a corpus with a ragged chunk tail, zero-variance level-0
+    segments on both sides, duplicate runs across chunks and a query count that is not a multiple of 64."""
     from hq_mi355x.core.search_engine import IndexCorpus
     rng = np.random.default_rng(77)
     N, L = 40_003, 64
@@ -264,27 +263,16 @@ def test_level0_scan_kernels_agree_and_match_oracle(hq_lib, hq_option):
     corpus = IndexCorpus(C)
     qp = corpus.prepare_queries(Q)
     res = {}
-    variants = {  # option settings of each variant (the default k_scan0g + k_sample_topg first)
+    variants = {  # option settings of each variant (the default first)
         "v0": {},
-        "v0-nosample": {"scan_nosample": 1},
-        "v0-wpb4-pf3": {"scan_wpb": 4, "scan_pf": 3},
-        "v0-pf4": {"scan_pf": 4},  # (the default scan is 3 waves per SIMD with 6 steps of prefetch)
-        "v0-nb8": {"scan_nb": 8},  # 128-query waves
-        "v0-occ4-pf4": {"scan_occ": 4, "scan_pf": 4},  # round 5's 4 waves per SIMD, 4096-wave geometry
-        "v0-occ3-pf8": {"scan_occ": 3, "scan_pf": 8},
-        "v0-occ3-pf4": {"scan_occ": 3, "scan_pf": 4},
-        "v0-sample-full": {"sample_variant": 1},
-        "v0-list": {"scan_variant": 1},  # k_scan0f
         "v1": {"scan_v1": 1},
     }
     for tag, opts in variants.items():
-        for name in ("scan_nosample", "scan_wpb", "scan_pf", "scan_nb", "scan_occ", "sample_variant", "scan_variant",
-                     "scan_v1"):
-            hq_option(name, opts.get(name))
+        hq_option("scan_v1", opts.get("scan_v1"))
         for thr, tm in ((0.1, 1), (0.6, 1), (0.1, 2)):
             sc, ids, cnt, _, _ = corpus.exact_topk(qp, 0, 20, thr, tm)
             res[(tag, thr, tm)] = (_np(sc), _np(ids), _np(cnt))
-        # M = 100 (a list of 108 > 64: every variant, scan_variant = 1 included, takes the queue scan)
+        # M = 100 (a list of 108 > 64)
         sc, ids, cnt, _, _ = corpus.exact_topk(qp, 0, 100, 0.1, 1)
         res[(tag, "m100", 1)] = (_np(sc), _np(ids), _np(cnt))
     for key in ((0.1, 1), (0.6, 1), (0.1, 2), ("m100", 1)):
@@ -607,10 +595,6 @@ def test_overall_split_scan_matches_f64_scan(hq_lib, hq_option, N, L):
     sc, ids, _, _ = K_.scan_topk(qp, corpus.prep, 1, k + corpus.SLACK, -corpus.EPS, 0)
     _, _, _, res = K_.refine_topk(qp, corpus.prep, 1, sc, ids, k, 0.0, 0, corpus.EPS)
     assert int(_np(res).sum()) >= len(Q) - 2        # the dense fallback stays an exception
-    hq_option("ov_occ", 3)                         # the 3-waves-per-SIMD build of k_scanov
-    occ3 = [_np(x) for x in corpus.exact_topk(qp, 1, k)[:3]]
-    assert np.array_equal(got[1], occ3[1]) and np.array_equal(got[0], occ3[0])
-    hq_option("ov_occ", None)
     hq_option("scan_v1", 1)
     ref = [_np(x) for x in corpus.exact_topk(qp, 1, k)[:3]]
     assert np.array_equal(got[1], ref[1]) and np.array_equal(got[0], ref[0])

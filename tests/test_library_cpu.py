@@ -167,22 +167,45 @@ def test_kernel_options_are_explicit(lib):
     assert lib.hq_get_option(b"no_such_knob", None) == _lib.HQ_E_INVALID
 
 
-def _scan0f_reads(chunk_len: int, n_rows: int) -> int:
-    """Rows past its first that one k_scan0f wave reads for a chunk of n_rows rows (hq_search.hip k_scan0f:
-    two steps of 16 rows are loaded before the loop, each body loads one more step; the loop runs three
-    bodies while cs + 32 < c_end, then up to two tail bodies)."""
-    loads, cs = 2, 0
-    while cs + 32 < n_rows:
-        loads += 3
-        cs += 48
-    loads += (cs < n_rows) + (cs + 16 < n_rows)
-    return 16 * loads
+REMOVED_OPTIONS = (
+    "scan_variant", "scan_wpb", "scan_nb", "scan_pf", "scan_occ", "scan_split3", "scan_nosample", "scan_expt",
+    "refine_expt", "sample_variant", "sample_hi", "sample_stride", "sample_waves", "ov_occ", "ov_pf", "ov_waves",
+    "scanov_split3", "scanov_v1", "seg_prepare_flat", "final_rounds")
+KEPT_SEARCH_OPTIONS = (
+    "sample_kth", "scan_v1", "refine_global", "refine_coop", "refine_small", "select_2stage", "level_scores_v1",
+    "prep_coop", "pool_sort_mem", "rank_ct", "rank_win", "rank_sort_nt", "rank_sort_small")
 
 
-def test_scan0f_reads_stay_inside_padded_copies(lib):
-    """Deterministic guard for the round-2 fault class (prologue rows past the kPad0 padding): for every
-    corpus size N = 1..70,000 and query counts 1..1000, the largest Z16 / S32 row any k_scan0f wave reads
-    (chunks starting at or past N exit before loading) lies inside the padded copies."""
+def test_retired_scan_options_are_unknown_and_kept_ones_work(lib):
+    """The knobs of the retired scan variants are gone from the option table (setting one is an error, not a
+    silent no-op); every option the parity tests use to force a production path still sets, reads back and
+    resets."""
+    from hq_mi355x import _lib
+    for name in REMOVED_OPTIONS:
+        with pytest.raises(_lib.NativeLibraryError, match=f"unknown option '{name}'"):
+            _lib.set_option(name, 1)
+        assert lib.hq_get_option(name.encode(), None) == _lib.HQ_E_INVALID
+    for name in KEPT_SEARCH_OPTIONS:
+        assert _lib.get_option(name) is None, name
+        with _lib.option(name, 1):
+            assert _lib.get_option(name) == 1, name
+        assert _lib.get_option(name) is None, name
+
+
+def _scan0g_reads(n_rows: int) -> int:
+    """Rows from its first that one k_scan0g wave reads for a chunk holding n_rows rows (hq_search.hip k_scan0g):
+    nsteps = ceil(n_rows / 16) whole 16-row steps; the prologue loads steps min(u, nsteps - 1), each body loads
+    step min(s + PF, nsteps - 1) (the prefetch index is clamped to the chunk's last step), and the drain reads
+    the statistics of four rows inside a step it has scanned.  Code: hq_search.hip:1297 (nsteps), :1300 and
+    :1304 (the clamped prologue and body loads), :1181 (the drain's statistics group), :1129 (a chunk that
+    starts at or past N exits before any load)."""
+    return 16 * ((n_rows + 15) // 16)
+
+
+def test_scan0g_reads_stay_inside_padded_copies(lib):
+    """Deterministic guard for the round-2 fault class (rows read past the kPad0 padding): for every corpus size
+    N = 1..70,000 and query counts 1..1000, the largest Z16 / S32 row any k_scan0g wave reads (chunks starting
+    at or past N exit before loading) lies inside the padded copies, for the geometry that is launched."""
     g = [ctypes.c_int(), ctypes.c_int(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()]
     refs = [ctypes.byref(x) for x in g]
     worst = 0
@@ -192,11 +215,11 @@ def test_scan0f_reads_stay_inside_padded_copies(lib):
             nchunks, cl, z_rows, s_rows = g[1].value, g[2].value, g[3].value, g[4].value
             assert cl % 16 == 0 and nchunks % 8 == 0 and nchunks * cl >= N
             last = (N - 1) // cl                       # last chunk that starts below N
-            m = max(last * cl + _scan0f_reads(cl, N - last * cl) - 1,
-                    (last - 1) * cl + _scan0f_reads(cl, cl) - 1 if last > 0 else -1)
+            m = max(last * cl + _scan0g_reads(N - last * cl) - 1,
+                    (last - 1) * cl + _scan0g_reads(cl) - 1 if last > 0 else -1)
             assert m < z_rows and m < s_rows, (Q, N, m, z_rows)
             worst = max(worst, m - N)
-    assert worst == 46  # reads reach row N + 46: inside the 48 padding rows, 1 row to spare
+    assert worst == 14  # N = 1 (mod 16): the last step's 16 rows end at row N + 14, inside the 48 padding rows
 
 
 def test_bench_traffic_table_well_formed():

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of search-only bench lines under different environment settings, one box.
-# usage: tools/ab_search_env.sh "HQ_SAMPLE_STRIDE=16" "HQ_SAMPLE_STRIDE=32" ...
+# usage: tools/ab_search_env.sh "HQ_SAMPLE_KTH=0" "HQ_RANK_WIN=0" ...
 OUT=gpurun_out; mkdir -p $OUT
 i=0
 for rep in 1 2; do

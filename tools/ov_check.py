@@ -26,7 +26,7 @@ k = 10
 ds, di, _, _ = corpus._dense(qp, torch.arange(len(Qv), device=dev), 1, k, 0.0, 0)
 di = di.cpu()
 res = {}
-for tag, opts in (("lin", {}), ("v1", {"scanov_v1": 1})):
+for tag, opts in (("split", {}), ("v1", {"scan_v1": 1})):
     for n, v in opts.items():
         _lib.set_option(n, v)
     asc, aid, _, _ = K.scan_topk(qp, corpus.prep, 1, k + corpus.SLACK, -corpus.EPS, 0, 0)
@@ -38,6 +38,6 @@ for tag, opts in (("lin", {}), ("v1", {"scanov_v1": 1})):
     bad = [a for a in range(len(Qv)) if rs[a] and not torch.equal(ids[a], di[a])]
     res[tag] = aid.cpu()
     print(tag, "resolved", int(rs.sum()), "mismatch vs dense", len(bad), bad[:10], flush=True)
-A, B = res["lin"], res["v1"]
+A, B = res["split"], res["v1"]
 diff = [a for a in range(len(Qv)) if set(A[a].tolist()) != set(B[a].tolist())]
 print("raw candidate lists differ on", len(diff), "queries", diff[:10])

@@ -17,7 +17,7 @@ from collections import defaultdict
 vals = defaultdict(list)
 for f in glob.glob("gpurun_out/pmc_scan/**/*counter_collection.csv", recursive=True):
     for r in csv.DictReader(open(f)):
-        if "k_scan0f" in r["Kernel_Name"]:
+        if "k_scan0g" in r["Kernel_Name"]:
             vals[r["Counter_Name"]].append(float(r["Counter_Value"]))
 avg = {c: sum(x) / len(x) for c, x in vals.items()}
 w = avg.get("SQ_WAVES", 1)

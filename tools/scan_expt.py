@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Level-0 scan timing experiments: python tools/scan_expt.py [N] [Q]; HQ_SCAN_EXPT / HQ_SCAN_* env
-variables select kernel variants.  Prints ms per scan_topk call (k = 28, threshold 0.1)."""
+"""Level-0 scan timing: python tools/scan_expt.py [N] [Q]; SCAN_EXPT_ONLY=name[,name] picks variants.
+Prints ms per scan_topk call (k = 28, threshold 0.1)."""
 import os
 import sys
 import time
@@ -22,14 +22,14 @@ else:  # random walks
     C = torch.randn((N, 64), generator=g, device="cuda", dtype=torch.float64).cumsum(1) * 0.1
 corpus = IndexCorpus(C)
 qp = corpus.prepare_queries(C[:Q] + 0.01 * torch.randn((Q, 64), generator=g, device="cuda", dtype=torch.float64))
-VARIANTS = [("count", {"HQ_SCAN_EXPT": "3"}), ("default", {}),
-                  ("no-sample", {"HQ_SCAN_NOSAMPLE": "1"}), ("f64", {"HQ_SCAN_F64": "1"})]
+from hq_mi355x import _lib  # noqa: E402
+VARIANTS = [("default", {}), ("kth-k", {"sample_kth": 0})]  # option settings (hq_set_option)
 only = os.environ.get("SCAN_EXPT_ONLY")
-for name, env in VARIANTS:
+for name, opts in VARIANTS:
     if only and name not in only.split(","):
         continue
-    for k, v in env.items():
-        os.environ[k] = v
+    for k, v in opts.items():
+        _lib.set_option(k, v)
     K.scan_topk(qp, corpus.prep, 0, 28, 0.1, 1)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -37,5 +37,5 @@ for name, env in VARIANTS:
         K.scan_topk(qp, corpus.prep, 0, 28, 0.1, 1)
     torch.cuda.synchronize()
     print(f"{name:10s} {(time.perf_counter() - t0) / 5 * 1e3:8.3f} ms", flush=True)
-    for k in env:
-        del os.environ[k]
+    for k in opts:
+        _lib.reset_option(k)
