@@ -896,7 +896,12 @@ struct SampleArgs {
 // sum|.|, with sum|zq zc| <= m (Cauchy-Schwarz, sum z^2 = m): |dG| <= 2.1e-4 at m = 32; the score
 // moves by <= (0.65 / m) |dG| <= 4.3e-6; the f32 epilogue adds < 1e-6 (each term of num is bounded
 // by 0.6 rho_q rho_c <= 0.3 den).  The filter passes every pair within kMarginF of the threshold;
-// list scores are within ~5.5e-6 of the exact ones (callers re-rank with eps = 2e-5).  Vectors whose
+// list scores are within ~5.5e-6 of the exact ones (callers re-rank with eps = 2e-5).  Measured on the
+// MI355X over the adversarial families of tests/scan_contract.py (profiles/scan_error_bounds.txt; asserted
+// against the bound above by tests/test_gpu_scan_contract.py): 4.5e-7 at m = 32, 2.4e-7 at m = 16; the
+// overall split scan 1.8e-7; the f64 scan 2.2e-15.  These are the figures of the arithmetic as designed
+// with f16 subnormals kept (a NumPy model of it: 4.2e-7 / 1.7e-7; with them flushed it would be 1.3e-5 /
+// 1.7e-5, most lo halves being subnormal): the MFMA and dot2 f16 operands are not flushed.  Vectors whose
 // level-0 statistics are zero-variance or outside [2^-60, 2^60] (f32-unsafe) carry a flag and are
 // scored from the f64 statistics.
 // ------------------------------------------------------------------------------------------------
@@ -4062,6 +4067,10 @@ static int rs_for(int kp) {
   return r;
 }
 
+// k_scan's workgroup: the candidate tile, both sides' statistics, the score tile and 64 queries' lists.  With
+// 160 KiB of LDS per workgroup (gfx950) a 64-entry list fits level-0 segments of up to 64 values; the overall
+// mode of L = 64 stops at 57 entries, of L = 128 at 25 (kernels.scan_max_list repeats this sum for the callers)
+constexpr size_t kScanLdsMax = 160 * 1024;
 static size_t scan_lds_bytes(int rs, int nsu, int K) {
   return (size_t)8 * (kCB * rs + kCB * nsu * 4 + kQB * nsu * 4 + 4 * 16 * kCB + kQB * K) + (size_t)8 * kQB * K +
          (size_t)8 * kQB + (size_t)8 * kQB + (size_t)4 * kQB + 64;
@@ -4370,6 +4379,11 @@ __global__ __launch_bounds__(64) void k_seg_prepare_pack0_coop(const double* __r
 template <int KSMAX, bool OVERALL>
 static int launch_scan(const ScanArgs& a, hipStream_t s) {
   const size_t lds = scan_lds_bytes(a.rs, a.nseg_used, a.K);
+  // refused here, before any HIP call: a failed hipFuncSetAttribute also leaves its error behind for the next
+  // launch check of an unrelated call
+  if (lds > kScanLdsMax)
+    return fail(HQ_E_UNSUPPORTED, "a list of %d entries needs %zu bytes of LDS at this index length (<= %zu)", a.K, lds,
+                kScanLdsMax);
   HQ_CHECK_HIP(hipFuncSetAttribute((const void*)k_scan<KSMAX, OVERALL>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (int)lds));
   const int grid = a.nqb * a.nchunks;
@@ -4776,7 +4790,10 @@ __global__ void k_ov_qconst(const float* __restrict__ Sq, int Q, OvLayout o, con
     c.qB[i] = 0.6f * mn;
     c.qQ[i] = ms;
     c.qz[i] = z ? 1.0f : 0.0f;
-    float ia = 0.0f, be = 1.0f;
+    // a constant query segment scores up to 1.0 against a constant row segment, and that row's offset
+    // (packov_elem: - 0.25 w per zero-variance segment, sized for the 0.1 a varying query gets) comes off the
+    // bound whatever the query: 1.25 - 0.25 = 1.0
+    float ia = 0.0f, be = 1.25f;
     if (!z) {
       const float h = 0.5f / sqrtf(ms);
       ia = (o.gc1[i] + c.qA[i] * h) * (1.0f + 1e-5f);
@@ -5076,11 +5093,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void k_
         float G[4] = {0.0f, 0.0f, 0.0f, 0.0f};
         ov_split_g<T>(a.Zq, a.Zc, q, row, G);
         const float s = ov_model<NG, NC>(o, c, a.Sc32, row, G, a.Sq, a.Sc, q);
+        // s = -1: a flagged row, which k_scanov_flagged scores; without a threshold (thl = -inf) the
+        // comparison with thl alone would list it here too, a second time and with score -1
+        const bool pass = s >= 0.0f && s >= c.thl;
         if constexpr (LIN) {
-          ok = s >= c.thl;
+          ok = pass;
           sv = s;
           rk = (int)((row - c_begin) << 5) | eqi;
-        } else if (s >= c.thl) {
+        } else if (pass) {
           const int slot = atomicAdd(a.pool_n + q, 1);
           if (slot < a.pool_cap) {
             a.pool_s[(int64_t)q * a.pool_cap + slot] = s;
@@ -5461,6 +5481,27 @@ static int ov_launch(const OvArgs& a0, const OvPlan& p, const SegInfo& si, int k
   return HQ_OK;
 }
 
+// the scans' answer for an empty corpus: (-inf, -1) in every list slot, and for the arg-max
+__global__ __launch_bounds__(256) void k_empty_lists(double* __restrict__ score, int64_t* __restrict__ id, int64_t n,
+                                                     double* __restrict__ best, int64_t* __restrict__ best_id, int Q) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    score[i] = -__builtin_huge_val();
+    id[i] = -1;
+    if (i < Q) {
+      if (best) best[i] = -__builtin_huge_val();
+      if (best_id) best_id[i] = -1;
+    }
+  }
+}
+
+static int empty_lists(double* score, int64_t* id, int Q, int k, double* best, int64_t* best_id, hipStream_t s) {
+  const int64_t n = (int64_t)Q * k, nb = (n + 255) / 256;  // n >= Q: the lists cover the arg-max entries
+  hipLaunchKernelGGL(k_empty_lists, dim3((unsigned)(nb < 4096 ? nb : 4096)), dim3(256), 0, s, score, id, n, best,
+                     best_id, Q);
+  HQ_CHECK_LAUNCH();
+  return HQ_OK;
+}
+
 }  // namespace hq
 
 using namespace hq;
@@ -5695,11 +5736,7 @@ int hq_scan_topk(const double* Zq, const double* Sq, int Q, const double* Zc, co
   if (Q == 0) return HQ_OK;
   if (!out_score || !out_id) return fail(HQ_E_INVALID, "null buffer");
   hipStream_t s = (hipStream_t)stream;
-  if (N == 0) {
-    HQ_CHECK_HIP(hipMemsetAsync(out_id, 0xFF, sizeof(int64_t) * Q * k, s));
-    if (out_best_id) HQ_CHECK_HIP(hipMemsetAsync(out_best_id, 0xFF, sizeof(int64_t) * Q, s));
-    return HQ_OK;
-  }
+  if (N == 0) return empty_lists(out_score, out_id, Q, k, out_best, out_best_id, s);
   if (!Zq || !Sq || !Zc || !Sc || !workspace) return fail(HQ_E_INVALID, "null buffer");
   if (workspace_bytes < hq_scan_workspace_size(Q, N, k)) return fail(HQ_E_INVALID, "workspace too small");
   ScanArgs a;
@@ -5817,10 +5854,7 @@ int hq_scan0_topk_split_fl(const void* Zq16, const float* Sq32, const double* Sq
   if (Q == 0) return HQ_OK;
   if (!out_score || !out_id) return fail(HQ_E_INVALID, "null buffer");
   hipStream_t s = (hipStream_t)stream;
-  if (N == 0) {
-    HQ_CHECK_HIP(hipMemsetAsync(out_id, 0xFF, sizeof(int64_t) * Q * k, s));
-    return HQ_OK;
-  }
+  if (N == 0) return empty_lists(out_score, out_id, Q, k, nullptr, nullptr, s);
   if (N >= 0x7FFFFFFF) return fail(HQ_E_UNSUPPORTED, "N=%lld rows (int32 row ids)", (long long)N);
   if (!Zq16 || !Sq32 || !Sq || !Zc16 || !Sc32 || !Sc || !workspace) return fail(HQ_E_INVALID, "null buffer");
   if (workspace_bytes < hq_scan_workspace_size(Q, N, k)) return fail(HQ_E_INVALID, "workspace too small");
@@ -6157,10 +6191,7 @@ int hq_scanov_topk_split(const void* Zq16, const float* Sq32, const double* Sq, 
   if (Q == 0) return HQ_OK;
   if (!out_score || !out_id) return fail(HQ_E_INVALID, "null buffer");
   hipStream_t s = (hipStream_t)stream;
-  if (N == 0) {
-    HQ_CHECK_HIP(hipMemsetAsync(out_id, 0xFF, sizeof(int64_t) * Q * k, s));
-    return HQ_OK;
-  }
+  if (N == 0) return empty_lists(out_score, out_id, Q, k, nullptr, nullptr, s);
   if (N >= 0x7FFFFFFF) return fail(HQ_E_UNSUPPORTED, "N=%lld rows (int32 row ids)", (long long)N);
   if (!Zq16 || !Sq32 || !Sq || !Zq || !Zc16 || !Sc32 || !Sc || !Zc || !workspace) return fail(HQ_E_INVALID, "null buffer");
   if (workspace_bytes < hq_scanov_workspace_size(Q, N, k)) return fail(HQ_E_INVALID, "workspace too small");

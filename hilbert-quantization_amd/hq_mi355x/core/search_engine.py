@@ -282,12 +282,15 @@ class IndexCorpus:
 
     def _max_list(self, mode: int) -> int:
         """Longest scan list (k + SLACK) the scan for `mode` takes: the split-f16 scans (level-0 copies for
-        mode 0, the overall layout for mode 1) up to MAX_SPLIT_K, the f64 scans up to MAX_FUSED_K."""
+        mode 0, the overall layout for mode 1) up to MAX_SPLIT_K, the f64 scans up to MAX_FUSED_K or what their
+        workgroup's LDS holds at this index length (K.scan_max_list: 57 for the overall mode of L = 64, 25 of
+        L = 128; a longer list takes the dense exact path, as every list past the scan's limit does)."""
+        fused = min(MAX_FUSED_K, K.scan_max_list(self.L, mode))
         if self.L % 2 or K._lib.get_option("scan_v1") is not None:
-            return MAX_FUSED_K
+            return fused
         if (mode == 0 and self.prep.Z16 is not None) or (mode == 1 and self.prep.Zov16 is not None):
             return MAX_SPLIT_K
-        return MAX_FUSED_K
+        return fused
 
     def key32(self, qp) -> bool:
         """Every vector float32 (query batch and corpus): the reference's sorts then compare numpy float32

@@ -475,6 +475,20 @@ def _workspace(nbytes: int, dev):
     return ws[:nbytes]
 
 
+@functools.lru_cache(maxsize=None)
+def scan_max_list(L: int, mode: int) -> int:
+    """Longest list (0 .. 64) hq_scan_topk takes at index length L (mode 0: level 0, 1: overall): its workgroup
+    keeps the candidate tile, both sides' statistics, the score tile and 64 queries' lists in 160 KiB of LDS
+    (scan_lds_bytes in hq_search.hip, repeated here; a longer list is refused with HQ_E_UNSUPPORTED)."""
+    cols = seg_level0_len(L) if mode == 0 else seg_padded_len(L)
+    nsu = 1 if mode == 0 else seg_count(L)
+    rs = max(cols, 2)
+    while rs % 32 != 2:
+        rs += 1
+    fixed = 8 * (64 * rs + 2 * 64 * nsu * 4 + 4 * 16 * 64) + 2 * 8 * 64 + 4 * 64 + 64
+    return max(0, min(64, (160 * 1024 - fixed) // (16 * 64)))
+
+
 def scan_topk(q: Prepared, c: Prepared, mode: int, k: int, threshold: float = 0.0, thr_mode: int = 0,
               id_base: int = 0, need_best: bool = False, exc=None):
     """Fused MFMA scan + per-query top-k on APPROXIMATE scores.  mode 0: level-0 score, 1: overall.

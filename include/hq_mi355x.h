@@ -207,7 +207,11 @@ int hq_level_scores(const double* Rq, const double* Zq, const double* Sq, int Q,
  * video hierarchical scan, core/video_search.py:215-264); mode 1: overall score
  * (brute_force_search :302-338).  thr_mode 0: keep all; 1: score >= threshold; 2: > threshold.
  * Also the first arg-max of the approximate score (out_best, may be NULL).  id_base is added to
- * local row ids (sharding).  out_score/out_id: Q x k (-inf / -1 in empty slots), 1 <= k <= 64.
+ * local row ids (sharding).  out_score/out_id: Q x k (-inf / -1 in empty slots), 1 <= k <= 64, and no
+ * longer than the workgroup's 160 KiB of LDS hold next to the candidate tile: 64 for level-0 segments of
+ * up to 64 values, 57 for the overall mode of L = 64 and the 128-value level 0 of L = 256, 25 for the
+ * overall mode of L = 128 (a longer list: HQ_E_UNSUPPORTED; callers take the dense exact path).
+ * Measured |score - exact| <= 2.2e-15 for L <= 256 (profiles/scan_error_bounds.txt).
  * The exact ranking is obtained with hq_refine_topk on a slightly larger list.  Vectors with an aux
  * bit 2 (unsafe) segment are outside the model: callers use the dense exact path for them.  Mode 0
  * without the arg-max and with a level-0 segment of <= 32 values runs an f64 wave-level kernel for
@@ -223,7 +227,8 @@ int hq_scan_topk(const double* Zq, const double* Sq, int Q, const double* Zc, co
  * Same result contract as hq_scan_topk(mode 0, no arg-max), but the contraction G = sum zq*zc runs as
  * a split-f16 product (z = hi + lo, G ~= hi.hi + hi.lo + lo.hi with f32 accumulation, three
  * v_mfma_f32_16x16x32_f16 per 16x16 tile) and the filter and list scores in f32.
- * |approx - exact| <= ~5.5e-6, so callers re-rank with hq_refine_topk at eps >= 2e-5.
+ * |approx - exact| <= ~5.5e-6 (measured: 4.5e-7 on adversarial inputs, profiles/scan_error_bounds.txt), so
+ * callers re-rank with hq_refine_topk at eps >= 2e-5.
  * hq_seg_pack0_split builds, from hq_seg_prepare's Z and S, Z16: f16 hi[32], lo[32] of the
  * zero-padded level-0 segment for round_up(N, 16) + 48 rows (128 B per row), in 16-row tiles of 2 KiB:
  * [hi: 64 x 8][lo: 64 x 8] halves, the 8 at (16 g + j) * 8 being row 16 t + j, values 8 g .. 8 g + 7
@@ -263,7 +268,9 @@ int hq_scan0_topk_split_fl(const void* Zq16, const float* Sq32, const double* Sq
 /* ---- S5 brute force: split-f16 overall scan ----------------------------------------------------
  * Replaces the per-candidate _calculate_overall_similarity loop of brute_force_search
  * (core/search_engine.py:302-338, :191-230) with one scan over all levels: approximate overall scores
- * (|approx - exact| <= ~6e-6) -> per-query top k, re-ranked exactly by hq_refine_topk (mode 1).
+ * (|approx - exact| <= ~6e-6; measured 1.8e-7) -> per-query top k, re-ranked exactly by hq_refine_topk
+ * (mode 1).  A query with an f32-unsafe segment is not scanned, and a query whose passing pairs overflow a
+ * wave's append buffer or its pool is given up: either list is (+inf, -1) throughout (unresolved).
  * hq_seg_packov_info: the layout of L's level segments (K-blocks of 32 values, segments of >= 2 values,
  * one-value segments, floats per statistics group of 4 rows); HQ_E_UNSUPPORTED when L has none (a
  * segment longer than 32 values, more than 4 / 2 of either kind, or another block pattern than the
