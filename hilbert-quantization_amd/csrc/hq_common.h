@@ -391,7 +391,13 @@ __device__ __forceinline__ int wsum64i(int v) {
 // hardware reciprocal, 1 ulp: |e3| <= 2^-23 and |y - y'| <= 255 * 6 * 2^-24 < 9.2e-5).  Hence
 // trunc(y') == trunc(y) whenever frac(y') lies in [1e-4, 1 - 1e-4] (frac is exact: y' - floor(y')
 // for y' < 2^23); otherwise `slow` is set and the caller recomputes that element with the exact
-// division.
+// division.  The ei are relative errors, so the bound needs fl(1/rng) and fl(fl(1/rng) * 255) (the packed
+// form of k_chunk_np and process_emb multiplies by that product) to be normal float32 numbers: for rng
+// below about 7.5e-37 the product is inf, y' is inf or NaN and the guard compares false; for rng near
+// FLT_MAX the reciprocal is subnormal and e3 is unbounded.  A caller therefore takes the reciprocal form
+// only when recip_ok(rng) and the exact division otherwise.  f16 data (k_chunk_np) cannot leave that
+// window: a frame that is not flat has 2^-24 <= rng <= 131008.
+__host__ __device__ inline bool recip_ok(float rng) { return rng >= 0x1p-100f && rng <= 0x1p100f; }
 __device__ __forceinline__ uint32_t qfast(float x, float mn, float rcp, bool& slow) {
   const float y = ((x - mn) * rcp) * 255.0f;
   const float fl = floorf(y);

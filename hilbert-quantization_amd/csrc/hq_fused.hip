@@ -238,7 +238,8 @@ __device__ __forceinline__ void process_emb(int64_t e, const Buf<NS, ND>& b, int
         if constexpr ((V & 2) != 0) {
           // packed f32 pairs: y = (x - mn) * fl(fl(1/rng) * 255) (qfast's < 7.7e-5 bound), floor(y)
           // placed straight into its 2x2-block byte by v_cvt_pk_u8_f32; the exact division only at an
-          // element position where some lane's y lies within 1e-4 of an integer
+          // element position where some lane's y lies within 1e-4 of an integer, and everywhere when rng
+          // is outside the window in which the bound holds (recip_ok: c255 would be inf or imprecise)
           typedef float f2v __attribute__((ext_vector_type(2)));
           const f2v mn2 = {mn, mn}, c2 = {c255, c255}, h2 = {0.5f, 0.5f};
           const f2v ya = (f2v{x.x, x.y} - mn2) * c2, yb = (f2v{x.z, x.w} - mn2) * c2;
@@ -251,8 +252,10 @@ __device__ __forceinline__ void process_emb(int64_t e, const Buf<NS, ND>& b, int
             fb.y = q0f;
           }
           const float xs[4] = {x.x, x.y, x.z, x.w};
-          const bool sl[4] = {fabsf(ta.x) > 0.4999f, fabsf(ta.y) > 0.4999f && 4 * j + 1 < d,
-                              fabsf(tb.x) > 0.4999f && 4 * j + 2 < d, fabsf(tb.y) > 0.4999f && 4 * j + 3 < d};
+          const bool ex = !recip_ok(rng);
+          const bool sl[4] = {ex || fabsf(ta.x) > 0.4999f, (ex || fabsf(ta.y) > 0.4999f) && 4 * j + 1 < d,
+                              (ex || fabsf(tb.x) > 0.4999f) && 4 * j + 2 < d,
+                              (ex || fabsf(tb.y) > 0.4999f) && 4 * j + 3 < d};
           const uint32_t p0 = code & 3u, p1 = (code >> 2) & 3u, p2 = (code >> 4) & 3u, p3 = (code >> 6) & 3u;
           w = __builtin_amdgcn_cvt_pk_u8_f32(fa.x, p0, 0u);
           w = __builtin_amdgcn_cvt_pk_u8_f32(fa.y, p1, w);

@@ -402,11 +402,11 @@ __global__ __launch_bounds__(64 * WPB) void k_chunk_np(const uint16_t* __restric
   const bool flat = mx == mn;
   const float rng = mx - mn;
   // hardware reciprocal (1 ulp; the fast form's bound with it: qfast, hq_common.h); f16 data gives
-  // rng >= 2^-24 or a flat frame, so 1 / rng stays finite
+  // 2^-24 <= rng <= 131008 or a flat frame, so 1 / rng and 255 / rng are normal numbers (recip_ok holds)
   const float rcp = __builtin_amdgcn_rcpf(rng);
   uint8_t* dst = frame_out + c * FB;
   // one quantized byte: reciprocal form with an exact fallback per cell position (qfast, hq_common.h)
-  // — the IEEE division runs only where some lane's value lies within 1e-3 of a level edge
+  // — the IEEE division runs only where some lane's y lies within 1e-4 of an integer
   auto qb = [&](float x) -> uint32_t {
     if constexpr (FQ) {
       bool slow = false;

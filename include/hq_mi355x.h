@@ -135,7 +135,15 @@ int hq_index_rag_f32(const float* img, int64_t N, int n, float* out, hq_stream_t
 /* ---- Q1/Q2: uint8 quantize / de-normalise ---------------------------------------------------
  * replaces core/compressor.py:256-280 _normalize_for_compression and :282-303
  * _denormalize_from_compression.  enh: f32 N x rows x cols; out u8 same shape;
- * minmax: f32 N x 2 (min, max) written.  Constant images give 128 everywhere.                  */
+ * minmax: f32 N x 2 (min, max) written.  Constant images give 128 everywhere.
+ *
+ * Input domain of every quantizer here (Q1, Q2, the fused kernel, the chunk encoder): all values are
+ * finite and max - min of an image is finite (it does not overflow float32).  Inside that domain the
+ * bytes are bit-identical to the reference's float32 trunc((x - min) / (max - min) * 255), subnormal
+ * values and ranges included (float32 and f16 subnormals are kept, not flushed).  A NaN or Inf in an
+ * image, or a range whose difference overflows, gives unspecified bytes and min / max, as in the
+ * reference, whose astype(uint8) of NaN is undefined.  Q2 likewise takes finite min <= max with a
+ * finite difference.                                                                            */
 int hq_quantize_u8(const float* enh, int64_t N, int rows, int cols, uint8_t* out, float* minmax,
                    hq_stream_t stream);
 int hq_dequantize_u8(const uint8_t* u8, int64_t N, int rows, int cols, const float* minmax,
@@ -146,14 +154,20 @@ int hq_dequantize_u8(const uint8_t* u8, int64_t N, int rows, int cols, const flo
  * pad (:325-349) -> map_to_2d -> streaming index (L) -> embed_indices_in_image
  * (core/index_generator.py:221-253) -> _normalize_for_compression.
  * in: f32 N x d (row stride in_stride elements), d <= n*n, 2 <= n <= 128;
- * frame: u8 N x (n+1) x n; idx: f64 N x L (may be NULL); minmax: f32 N x 2 (may be NULL).      */
+ * frame: u8 N x (n+1) x n; idx: f64 N x L (may be NULL); minmax: f32 N x 2 (may be NULL).
+ * Input domain: as for Q1 (finite values, finite max - min over the padded row and its index row). */
 int hq_map_index_quantize(const float* in, int64_t N, int64_t in_stride, int d, int n, int L,
                           uint8_t* frame, double* idx, float* minmax, hq_stream_t stream);
 
 /* ---- config 5: f16 parameter stream, chunked (core/streaming_processor.py:539-582,877-972) ---
  * Consecutive chunks of `chunk` fp16 values (the last may be shorter, >= chunk/2) are each padded
  * to n*n (n = side of chunk), Hilbert-mapped, given the TRADITIONAL index (L = min(chunk, n)),
- * embedded and quantized: frame u8 nchunks x (n+1) x n, idx f32 nchunks x L, minmax f32 x 2.     */
+ * embedded and quantized: frame u8 nchunks x (n+1) x n, idx f32 nchunks x L, minmax f32 x 2.
+ * A shorter last chunk gets the geometry of its own length (side ts <= n): its frame is the first
+ * (ts+1)*ts bytes of the last slot and its index the first ts values; the rest of that slot is not
+ * written.  A `chunk` of 5..64 values (side 4 or 8) has frames that are no multiple of 16 bytes:
+ * HQ_E_UNSUPPORTED, nothing written (a tail of that size inside a larger slot is fine).  Input domain: finite f16 values (as for Q1; every finite f16
+ * range is inside it).                                                                            */
 int hq_chunk_encode_f16(const uint16_t* in, int64_t total, int chunk, uint8_t* frame, float* idx,
                         float* minmax, hq_stream_t stream);
 
