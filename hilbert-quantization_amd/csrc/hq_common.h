@@ -53,6 +53,7 @@ enum Opt {
   OPT_PRECOMP_WS, OPT_PRECOMP_LEAF_ROT, OPT_PRECOMP_ORDER, OPT_PRECOMP_G2REG,
   OPT_REFINE_COOP, OPT_PRECOMP_COMPACT, OPT_PREP_COOP, OPT_POOL_SORT_MEM, OPT_REFINE_SMALL,
   OPT_RANK_CT, OPT_RANK_WIN, OPT_RANK_SORT_NT, OPT_RANK_SORT_SMALL,
+  OPT_DECODE_NT, OPT_DECODE_GENERIC,
   OPT_COUNT
 };
 int64_t opt(Opt id, int64_t dflt);

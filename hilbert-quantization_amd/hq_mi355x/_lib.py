@@ -62,6 +62,8 @@ SIGNATURES = {
     "hq_quantize_u8": (_i, [_p, _i64, _i, _i, _p, _p, _p]),
     "hq_dequantize_u8": (_i, [_p, _i64, _i, _i, _p, _p, _p]),
     "hq_map_index_quantize": (_i, [_p, _i64, _i64, _i, _i, _i, _p, _p, _p, _p]),
+    "hq_dequantize_unmap": (_i, [_p, _i64, _i, _i, _p, _i, _p, _i64, _p, _p, _p]),
+    "hq_roundtrip_error": (_i, [_p, _i64, _p, _i64, _i64, _i, _p, _p]),
     "hq_chunk_encode_f16": (_i, [_p, _i64, _i, _p, _p, _p, _p]),
     "hq_parse_structure": (_i, [_i, _p, _i]),
     "hq_seg_count": (_i, [_i]),

@@ -144,8 +144,8 @@ class HilbertQuantizer:
             raise ReconstructionError(f"Unexpected error during reconstruction: {e}") from e
 
     def reconstruct_many(self, quantized_models: List[QuantizedModel], validate: bool = True) -> List[np.ndarray]:
-        """reconstruct() for many models: host JPEG decode on threads, one de-normalise and one inverse
-        Hilbert gather per frame shape (core.pipeline.reconstruct_batch); same arrays and errors."""
+        """reconstruct() for many models: host JPEG decode on threads, one fused de-normalise + inverse Hilbert
+        gather launch per frame shape (core.pipeline.reconstruct_batch); same arrays and errors."""
         from .core.pipeline import reconstruct_batch
         try:
             out = reconstruct_batch(quantized_models, self.quantization_pipeline.compressor)
@@ -378,6 +378,19 @@ class BatchQuantizer:
     def quantize_device(self, parameters, index_space_size: Optional[int] = None):
         """f32 [N, d] -> (frames u8 [N, n+1, n], indices f64 [N, L], minmax f32 [N, 2]) on the GPU."""
         return quantize_batch(parameters, self.quantizer.min_efficiency_ratio, index_space_size)
+
+    @staticmethod
+    def reconstruct_device(frames, minmax, parameter_count: int):
+        """The inverse of quantize_device on the GPU: (frames u8 [N, n+1, n], minmax f32 [N, 2] or one shared
+        pair) -> parameters f32 [N, parameter_count], one fused launch (core.pipeline.reconstruct_frames_batch)."""
+        from .core.pipeline import reconstruct_frames_batch
+        return reconstruct_frames_batch(frames, minmax, parameter_count)
+
+    @staticmethod
+    def extract_indices_device(frames, minmax):
+        """Batched extract_indices_from_image on the GPU: (index rows f32 [N, n], kept lengths int32 [N])."""
+        from .core.pipeline import extract_indices_batch
+        return extract_indices_batch(frames, minmax)
 
     @staticmethod
     def build_corpus(indices, id_base: int = 0) -> IndexCorpus:

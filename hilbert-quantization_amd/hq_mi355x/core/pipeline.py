@@ -115,18 +115,84 @@ class QuantizationPipeline:
         except Exception as e:
             raise HilbertQuantizationError(f"Failed to reconstruct parameters: {e}")
 
+    def validate_quantization(self, original_parameters, quantized_model: QuantizedModel,
+                              tolerance: float = 1e-3) -> Dict[str, Any]:
+        """core/pipeline.py:237-296: reconstruct and compare.  mse / mae / max_error are the reference's
+        float32 NumPy expressions (:257-259) evaluated by hq_roundtrip_error, bit for bit, returned as
+        Python floats; any failure gives the reference's failure dictionary."""
+        try:
+            reconstructed = self.reconstruct_parameters(quantized_model)
+            o = np.asarray(original_parameters)
+            r = np.asarray(reconstructed)
+            if o.dtype != np.float32 or r.dtype != np.float32 or o.ndim != 1:
+                raise TypeError(f"GPU round-trip metrics implement the float32 path, got {o.dtype} and {r.dtype}")
+            if o.shape != r.shape:  # the reference fails here too (NumPy cannot broadcast the difference)
+                raise ValueError(f"original parameters {o.shape} and reconstruction {r.shape} differ in shape")
+            mse, mae, max_error = (float(v) for v in to_np(K.roundtrip_error(to_dev(o), to_dev(r),
+                                                                             HilbertQuantizationError)))
+            results = {
+                "is_valid": mse <= tolerance,
+                "mse": mse,
+                "mae": mae,
+                "max_error": max_error,
+                "tolerance": tolerance,
+                "parameter_count_match": len(r) == len(o),
+                "compression_ratio": quantized_model.metadata.compression_ratio,
+                "original_size_bytes": quantized_model.metadata.original_size_bytes,
+                "compressed_size_bytes": quantized_model.metadata.compressed_size_bytes,
+            }
+            get_metrics = getattr(self.compressor, "get_last_compression_metrics", None)
+            metrics = get_metrics() if get_metrics is not None else None
+            if metrics:
+                results.update({"compression_time": metrics.compression_time_seconds,
+                                "decompression_time": metrics.decompression_time_seconds,
+                                "memory_usage_mb": metrics.memory_usage_mb})
+            return results
+        except Exception as e:
+            return {"is_valid": False, "error": str(e), "mse": float("inf"), "mae": float("inf"),
+                    "max_error": float("inf")}
+
+
+def reconstruct_frames_batch(frames, minmax, parameter_count: int):
+    """Device-resident inverse of quantize_batch: u8 frames [N, n+1, n] with their (min, max) ([N, 2], or one
+    [2] / [1, 2] pair for every frame) -> f32 parameters [N, parameter_count] on the device, in ONE kernel
+    (hq_dequantize_unmap: de-normalise, drop the index row, inverse Hilbert gather, truncate).  The values
+    are those of QuantizationPipeline.reconstruct_parameters (core/pipeline.py:183-235) on the same frame
+    bytes; a parameter_count above n * n raises the reference's count-mismatch error."""
+    fr = to_dev(frames)
+    if fr.dim() == 2:
+        fr = fr.unsqueeze(0)
+    n = int(fr.shape[-1])
+    parameter_count = int(parameter_count)
+    if parameter_count > n * n:
+        raise HilbertQuantizationError(
+            f"Failed to reconstruct parameters: Reconstructed parameter count {n * n} doesn't match "
+            f"original {parameter_count}")
+    return K.dequantize_unmap(fr, to_dev(minmax), parameter_count, exc=HilbertQuantizationError)
+
+
+def extract_indices_batch(frames, minmax):
+    """Batched extract_indices_from_image (core/index_generator.py:255-290) of u8 frames [N, n+1, n] on the
+    device: (index rows f32 [N, n], kept lengths int32 [N]); row e's indices are rows[e, :lengths[e]]."""
+    fr = to_dev(frames)
+    if fr.dim() == 2:
+        fr = fr.unsqueeze(0)
+    _, rows, lens = K.dequantize_unmap(fr, to_dev(minmax), 0, want_index=True, exc=HilbertQuantizationError)
+    return rows, lens
+
 
 def reconstruct_batch(models, compressor: MPEGAICompressorImpl, workers: int = 16):
     """Batched QuantizationPipeline.reconstruct_parameters (core/pipeline.py:183-235) for
-    many QuantizedModels: the JPEG payloads decode on a host thread pool (the codec), then per frame shape
-    ONE de-normalise launch (hq_dequantize_u8, with the compressor instance's last (min, max) for every
-    model, exactly as the per-model path reads that shared state) and ONE inverse-Hilbert gather
-    (hq_map_from_2d) of the image rows above the index row; each model's vector is truncated to its
-    parameter count.  Returns float32 NumPy vectors in model order; the errors are the per-model path's
-    (HilbertQuantizationError wrapping the decompress / shape failure of the first failing model)."""
+    many QuantizedModels: the JPEG payloads decode on a host thread pool (the codec), then every group of
+    (n + 1) x n frames takes ONE fused launch (hq_dequantize_unmap: de-normalise with the compressor
+    instance's last (min, max) for every model, exactly as the per-model path reads that shared state, drop
+    the index row, inverse Hilbert gather) of the group's largest parameter count, so the host receives
+    [members, d] floats; each model's vector is truncated to its own count.  Frames of another shape are
+    left to the per-model path (None).  Returns float32 NumPy vectors in model order; the errors are the
+    per-model path's (HilbertQuantizationError wrapping the decompress / shape failure of the first failing
+    model)."""
     import concurrent.futures as cf
     from .compressor import check_payload, decode_jpeg
-    t = torch()
     models = list(models)
     out = [None] * len(models)
 
@@ -143,24 +209,27 @@ def reconstruct_batch(models, compressor: MPEGAICompressorImpl, workers: int = 1
 
     with cf.ThreadPoolExecutor(max_workers=max(1, min(workers, len(models) or 1))) as pool:
         frames = list(pool.map(decode, range(len(models))))
-    mm = compressor._state_minmax()
+    mm = to_dev(compressor._state_minmax())
     groups = {}
     for i, f in enumerate(frames):
         groups.setdefault(f.shape, []).append(i)
     for shape, members in groups.items():
+        if len(shape) != 2 or shape[0] < 2 or shape[0] - 1 != shape[1] or (shape[1] & (shape[1] - 1)) != 0:
+            continue  # not an (n + 1) x n enhanced frame: per-model path
+        c = shape[1]
+        d = min(max(max(int(models[i].parameter_count) for i in members), 0), c * c)
         u8 = to_dev(np.stack([frames[i] for i in members]))
-        enh = K.dequantize_u8(u8, to_dev(np.repeat(mm[None], len(members), 0)), HilbertQuantizationError)
-        r, c = shape
-        if r < 2 or r - 1 != c or (c & (c - 1)) != 0:  # not an (n + 1) x n enhanced frame: per-model path
-            for i in members:
-                out[i] = None
-            continue
-        flat = to_np(K.map_from_2d(enh[:, :-1, :].contiguous(), None, HilbertQuantizationError))
+        if 2 <= c <= 128:
+            flat = to_np(K.dequantize_unmap(u8, mm, d, exc=HilbertQuantizationError))
+        else:  # sides the fused kernel does not take (1, above 128): de-normalise, then the generic gather
+            enh = K.dequantize_u8(u8, mm.view(1, 2).expand(len(members), 2), HilbertQuantizationError)
+            flat = to_np(K.map_from_2d(enh[:, :-1, :].contiguous(), d, HilbertQuantizationError))
         for k, i in enumerate(members):
-            v = flat[k, : models[i].parameter_count]
-            if len(v) != models[i].parameter_count:
+            pc = models[i].parameter_count
+            got = len(range(c * c)[:pc])  # length of the padded c * c vector's [:pc]
+            if got != pc:
                 raise HilbertQuantizationError(
-                    f"Failed to reconstruct parameters: Reconstructed parameter count {len(v)} doesn't match "
-                    f"original {models[i].parameter_count}")
-            out[i] = v.copy()
+                    f"Failed to reconstruct parameters: Reconstructed parameter count {got} doesn't match "
+                    f"original {pc}")
+            out[i] = flat[k, :pc].copy()
     return out

@@ -184,6 +184,70 @@ def map_index_quantize(x, n: int, L: Optional[int] = None, want_idx: bool = True
     return frames, idx, mm
 
 
+def dequantize_unmap(frames, minmax, d: Optional[int] = None, want_index: bool = False, out=None, exc=None):
+    """The fused decode: u8 frames [N, n+1, n] (or [n+1, n]) -> f32 parameters [N, d] in curve order, i.e.
+    map_from_2d(dequantize_u8(frames)[:, :-1])[:, :d] in ONE kernel (core/pipeline.py:183-235 after the codec).
+
+    minmax: f32 device tensor [N, 2], or ONE pair of shape [2] / [1, 2] applied to every frame (shared mode:
+    the compressor-state semantics of core/compressor.py:282-303).  d defaults to n * n.  out: an f32 device
+    tensor [N, >= d] with unit column stride to write into (its columns from d on are left as they are).
+    want_index: also return the de-normalised index rows f32 [N, n] and the lengths int32 [N] that
+    extract_indices_from_image keeps (core/index_generator.py:255-290)."""
+    t = torch()
+    squeeze = frames.dim() == 2
+    fr = _contig(frames.unsqueeze(0) if squeeze else frames)
+    if fr.dtype != t.uint8:
+        raise TypeError("dequantize_unmap expects uint8 frames")
+    N, r, n = fr.shape
+    if r != n + 1:
+        raise ValueError(f"dequantize_unmap expects (n + 1) x n frames, got {r} x {n}")
+    if d is None:
+        d = n * n
+    d = int(d)
+    mm = minmax if minmax.dtype == t.float32 else minmax.to(t.float32)
+    shared = mm.dim() == 1 or (mm.shape[0] == 1 and N != 1)
+    mm = _contig(mm.reshape(-1, 2))
+    if not shared and mm.shape[0] != N:
+        raise ValueError(f"minmax must be [2], [1, 2] or [{N}, 2], got {tuple(minmax.shape)}")
+    if out is None:
+        out = t.empty((N, d), dtype=t.float32, device=fr.device)
+    elif (out.dtype != t.float32 or out.dim() != 2 or out.shape[0] != N or out.shape[1] < d
+          or (out.shape[1] > 1 and out.stride(1) != 1)):
+        raise ValueError(f"out must be a float32 [{N}, >= {d}] tensor with unit column stride")
+    stride = out.stride(0) if N > 1 else max(int(out.shape[1]), d)
+    idx_row = t.empty((N, n), dtype=t.float32, device=fr.device) if want_index else None
+    idx_len = t.empty((N,), dtype=t.int32, device=fr.device) if want_index else None
+    _chk(_L().hq_dequantize_unmap(ptr(fr), N, n, d, ptr(mm), 1 if shared else 0, ptr(out), stride, ptr(idx_row),
+                                  ptr(idx_len), stream()), exc)
+    params = out if out.shape[1] == d else out[:, :d]
+    if squeeze:
+        return (params[0], idx_row[0], idx_len[0]) if want_index else params[0]
+    return (params, idx_row, idx_len) if want_index else params
+
+
+def roundtrip_error(orig, recon, exc=None):
+    """f32 [N, d] (or [d]) original and reconstructed rows -> f32 [N, 3] (or [3]) = (mse, mae, max_error) per
+    row: np.mean((o - r) ** 2), np.mean(np.abs(o - r)), np.max(np.abs(o - r)) bit for bit
+    (core/pipeline.py:257-259 validate_quantization)."""
+    t = torch()
+    squeeze = orig.dim() == 1
+    o = orig.view(1, -1) if squeeze else orig
+    r = recon.view(1, -1) if recon.dim() == 1 else recon
+    if o.dtype != t.float32 or r.dtype != t.float32:
+        raise TypeError("roundtrip_error expects float32 rows")
+    if tuple(o.shape) != tuple(r.shape):
+        raise ValueError(f"shapes differ: {tuple(o.shape)} and {tuple(r.shape)}")
+    if o.stride(-1) != 1:
+        o = o.contiguous()
+    if r.stride(-1) != 1:
+        r = r.contiguous()
+    N, d = o.shape
+    out = t.empty((N, 3), dtype=t.float32, device=o.device)
+    _chk(_L().hq_roundtrip_error(ptr(o), o.stride(0) if N > 1 else d, ptr(r), r.stride(0) if N > 1 else d, N, d,
+                                 ptr(out), stream()), exc)
+    return out[0] if squeeze else out
+
+
 def chunk_encode_f16(x, chunk: int = 1024, exc=None, out=None):
     """Config 5: flat f16 stream -> per-chunk (u8 frame, f32 traditional index, minmax)
     (core/streaming_processor.py:539-582, 877-913).  The last (shorter) chunk uses its own

@@ -57,7 +57,9 @@ const char* hq_last_error(void);
  * "sample_kth" (0 = provable bound), "scan_v1" (the LDS-tiled f64 scans instead of the split-f16 ones),
  * "rank_ct" (0: the long-list re-rank's runtime level structure; 2: the compile-time one in the short-list kernel too),
  * "rank_win" (0: the long-list ranking by the bitonic sort alone, no window ranking), "rank_sort_nt" (512: lists
- * > 512 in 512-thread workgroups), "rank_sort_small" (0: lists <= 128 in the 1024-entry workgroup).  Options are
+ * > 512 in 512-thread workgroups), "rank_sort_small" (0: lists <= 128 in the 1024-entry workgroup), "decode_nt"
+ * (0: plain instead of non-temporal stores in hq_dequantize_unmap), "decode_generic" (1: its generic kernel
+ * for every n).  Options are
  * process-wide: set them before launching, not
  * while other host threads launch.  hq_reset_option restores the default; hq_get_option returns 1 when
  * the option is set (value in *value), 0 when it is at its default, HQ_E_INVALID for an unknown name.
@@ -158,6 +160,33 @@ int hq_dequantize_u8(const uint8_t* u8, int64_t N, int rows, int cols, const flo
  * Input domain: as for Q1 (finite values, finite max - min over the padded row and its index row). */
 int hq_map_index_quantize(const float* in, int64_t N, int64_t in_stride, int d, int n, int L,
                           uint8_t* frame, double* idx, float* minmax, hq_stream_t stream);
+
+/* ---- fused de-normalise + index-row extract + 2-D -> 1-D gather (the decode of the kernel above) ----
+ * replaces the component sequence of core/pipeline.py:183-235 reconstruct_parameters after the codec:
+ * _denormalize_from_compression (core/compressor.py:282-303) -> extract_indices_from_image
+ * (core/index_generator.py:255-290) -> map_from_2d (core/hilbert_mapper.py:176-205) -> [:d].
+ * frame: u8 N x (n+1) x n contiguous, index row last; minmax: f32 N x 2, or ONE (min, max) pair applied to
+ * every frame when mm_shared != 0 (the compressor instance's state, core/compressor.py:282-303; (0, 1) is
+ * the stateless u8 / 255).  out: f32 N rows of d values, rows out_stride >= d floats apart:
+ * out[e][i] = the de-normalised cell at curve position i, i < d <= n*n (d = 0 allowed); floats d ..
+ * out_stride - 1 of a row are not written.  idx_row (f32 N x n, may be NULL): the de-normalised last row;
+ * idx_len (int32 N, may be NULL): the length extract_indices_from_image keeps, 1 + the position of the
+ * last value != 0.0f (-0.0 counts as zero, as in np.nonzero), 1 when there is none.
+ * Every value is (mx == mn) ? mn : ((float)b / 255.0f) * (mx - mn) + mn in float32 with the IEEE division:
+ * bit-identical to hq_dequantize_u8.  2 <= n <= 128; n in {16, 32, 64} with 16-byte aligned frames runs one
+ * wave per frame with 16-byte loads and stores (rows that are not 16-byte aligned: scalar stores).
+ * Input domain: as for Q2 (finite min <= max with a finite difference).                              */
+int hq_dequantize_unmap(const uint8_t* frame, int64_t N, int n, int d, const float* minmax, int mm_shared,
+                        float* out, int64_t out_stride, float* idx_row, int32_t* idx_len, hq_stream_t stream);
+
+/* ---- round-trip error metrics ------------------------------------------------------------------
+ * replaces the three expressions of core/pipeline.py:257-259 validate_quantization for N row pairs of d
+ * float32 values (row strides in floats): out f32 N x 3 = np.mean((o - r) ** 2), np.mean(np.abs(o - r)),
+ * np.max(np.abs(o - r)), bit-identical to NumPy on float32 arrays (elementwise float32, the means as
+ * f32(f64(pairwise f32 sum) / d) in NumPy's pairwise order).  1 <= d <= 2^26.  One thread per row walks
+ * that order serially: exact, not a throughput path.                                               */
+int hq_roundtrip_error(const float* orig, int64_t orig_stride, const float* recon, int64_t recon_stride,
+                       int64_t N, int d, float* out /* [N, 3]: mse, mae, max_error */, hq_stream_t stream);
 
 /* ---- config 5: f16 parameter stream, chunked (core/streaming_processor.py:539-582,877-972) ---
  * Consecutive chunks of `chunk` fp16 values (the last may be shorter, >= chunk/2) are each padded
