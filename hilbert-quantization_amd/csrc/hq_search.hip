@@ -4749,6 +4749,108 @@ __global__ __launch_bounds__(64) void k_seg_append(const double* __restrict__ id
   }
 }
 
+// n values of one row, copied by the nl lanes l = 0 .. nl - 1 of a wave: up to four loads per lane issued
+// before the first store, so a row of <= 4 nl values costs one round trip
+template <typename T>
+__device__ __forceinline__ void row_copy_t(T* dst, const T* src, int n, int l, int nl) {
+  for (int k0 = l; k0 < n; k0 += 4 * nl) {
+    T v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (k0 + u * nl < n) v[u] = src[k0 + u * nl];
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (k0 + u * nl < n) dst[k0 + u * nl] = v[u];
+  }
+}
+
+// n doubles of one row: 16-byte loads and stores where the row allows them (an even count at 16-byte aligned
+// addresses: every Z and statistics row of allocator-aligned buffers, R for even L)
+__device__ __forceinline__ void row_copy(double* dst, const double* src, int n, int l, int nl) {
+  if (!(n & 1) && !(((uintptr_t)dst | (uintptr_t)src) & 15))
+    row_copy_t(reinterpret_cast<f64x2*>(dst), reinterpret_cast<const f64x2*>(src), n >> 1, l, nl);
+  else
+    row_copy_t(dst, src, n, l, nl);
+}
+
+// Selecting M rows of a resident corpus into a second set of buffers (hq_seg_gather), one launch: one wave
+// per group of 4 destination rows (a statistics group of the split copies), 16 lanes per row.  The lanes of
+// destination row i copy source row src_row[i] (raw values when R is given, Z, statistics: functions of the
+// row alone, so nothing is recomputed); then the wave packs its 4 rows as k_seg_append packs one (pack0_elem,
+// packov_elem, flag_row, behind the same fence).  The groups past M write the pad rows up to z16_rows(M).
+// Four rows per wave keep four rows' loads in flight through the chain row number -> row -> fence -> pack,
+// which is latency, not bandwidth.  R / Z16 / Zo / flags may be null.
+__global__ __launch_bounds__(64) void k_seg_gather(const int64_t* __restrict__ src_row, int64_t M, int64_t N_src,
+                                                   SegInfo si, const double* __restrict__ R_src,
+                                                   const double* __restrict__ Z_src,
+                                                   const double* __restrict__ S_src, double* R, double* Z,
+                                                   double* stats, _Float16* Z16, float* S32, OvLayout o,
+                                                   _Float16* Zo, float* So, int* flags, int64_t groups) {
+  const int lane = threadIdx.x, rr = lane >> 4, ql = lane & 15;
+  const int per = o.nkb * 32, ns4 = si.nseg * 4;
+  for (int64_t g = blockIdx.x; g < groups; g += gridDim.x) {
+    const int64_t row0 = g * 4, row = row0 + rr;
+    if (row0 < M) {  // wave-uniform
+      if (row < M) {
+        int64_t sr = src_row[row];
+#ifdef HQ_DIAG
+        sr = diag_bound(sr, N_src, __LINE__);
+#endif
+        row_copy(Z + row * si.Lp, Z_src + sr * si.Lp, si.Lp, ql, 16);
+        row_copy(stats + row * ns4, S_src + sr * ns4, ns4, ql, 16);
+        if (R) row_copy(R + row * si.L, R_src + sr * si.L, si.L, ql, 16);
+      }
+      __threadfence_block();
+      __syncthreads();
+    }
+    if (Z16)
+      for (int t = lane; t < 4 * 32; t += 64) {
+        const int64_t r = row0 + (t >> 5);
+        pack0_elem(Z, stats, M, si.Lp, si.plen[0], si.nseg, Z16, S32, r, t & 31);
+        // this lane wrote the row's flag word (pack0_elem, value 0) just above
+        if (flags && (t & 31) == 0 && r < M) flag_row(S32, r, flags + 1, flags);
+      }
+    if (Zo)
+      for (int t = lane; t < 4 * per; t += 64) packov_elem(Z, stats, M, si.Lp, o, Zo, So, row0 + t / per, t % per);
+  }
+}
+
+// Overwriting M resident rows in place (hq_seg_replace): k_seg_append's steps per row (the segments from an
+// LDS copy, then the row's split level-0 and overall copies) for destination row rows[i] of the N resident
+// ones.  The layouts address by row, so every other row keeps its bytes; no pad row is written, and the
+// flagged-row list is rebuilt by k_flag_rows afterwards (a replaced row may enter or leave it).
+template <bool COOP>
+__global__ __launch_bounds__(64) void k_seg_replace(const double* __restrict__ idx, int64_t M,
+                                                    const int64_t* __restrict__ rows, int64_t N, SegInfo si,
+                                                    int all_f32, const uint8_t* __restrict__ row_f32, double* Z,
+                                                    double* stats, _Float16* Z16, float* S32, OvLayout o,
+                                                    _Float16* Zo, float* So) {
+  extern __shared__ double xs[];  // L values
+  const int lane = threadIdx.x;
+  const int per = o.nkb * 32;
+  for (int64_t i = blockIdx.x; i < M; i += gridDim.x) {
+    int64_t row = rows[i];
+#ifdef HQ_DIAG
+    row = diag_bound(row, N, __LINE__);
+#endif
+    const double* src = idx + i * si.L;
+    const bool is32 = row_f32 ? row_f32[i] != 0 : all_f32 != 0;
+    for (int k = lane; k < si.L; k += 64) xs[k] = src[k];
+    __syncthreads();
+    if (COOP) {
+      for (int sg = lane >> 3; sg < si.nseg; sg += 8) seg_prepare_coop(xs, row, sg, si, is32, Z, stats, lane & 7);
+    } else {
+      for (int sg = lane; sg < si.nseg; sg += 64) seg_prepare_one(xs, row, sg, si, is32, Z, stats);
+    }
+    __threadfence_block();
+    __syncthreads();
+    if (Z16 && lane < 32) pack0_elem(Z, stats, N, si.Lp, si.plen[0], si.nseg, Z16, S32, row, lane);
+    if (Zo)
+      for (int c = lane; c < per; c += 64) packov_elem(Z, stats, N, si.Lp, o, Zo, So, row, c);
+    __syncthreads();
+  }
+}
+
 // per-query constants of the overall scan (k_ov_qconst, from the query's Sov32 statistics and its
 // starting threshold); QOvD: the model's part, cached in LDS by k_scanov
 struct QOv {
@@ -6174,6 +6276,76 @@ int hq_seg_append(const double* idx, int64_t M, int L, int src_f32, const uint8_
                        flags);
   }
   HQ_CHECK_LAUNCH();
+  return HQ_OK;
+}
+
+int hq_seg_gather(const int64_t* src_row, int64_t M, int64_t N_src, int L, const double* R_src, const double* Z_src,
+                  const double* S_src, double* R, double* Z, double* stats, void* Z16, float* S32, void* Zov16,
+                  float* Sov32, int* flags, hq_stream_t stream) {
+  if (L <= 0 || M < 0 || N_src < 0 || (M > 0 && N_src == 0))
+    return fail(HQ_E_INVALID, "bad shape N_src=%lld M=%lld L=%d", (long long)N_src, (long long)M, L);
+  if (M >= 0x7FFFFFFF) return fail(HQ_E_UNSUPPORTED, "M=%lld rows (int32 row ids)", (long long)M);
+  if (M > 0 && (!src_row || !Z_src || !S_src || !Z || !stats)) return fail(HQ_E_INVALID, "null buffer");
+  if ((R_src == nullptr) != (R == nullptr)) return fail(HQ_E_INVALID, "the raw rows need both of their buffers");
+  if ((Z16 == nullptr) != (S32 == nullptr) || (Zov16 == nullptr) != (Sov32 == nullptr))
+    return fail(HQ_E_INVALID, "a split copy needs both of its buffers");
+  if (flags && !S32) return fail(HQ_E_INVALID, "the flagged-row list needs the level-0 copies");
+  SegInfo si;
+  seg_info(L, si);
+  if (si.nseg == 0) return fail(HQ_E_INVALID, "no level structure for L=%d", L);
+  if (Z16 && si.plen[0] > 32) return fail(HQ_E_INVALID, "level-0 copies with a level-0 segment of %d values", si.plen[0]);
+  OvLayout o = {};
+  if (Zov16 && !ov_layout(L, o)) return fail(HQ_E_INVALID, "overall copies without a split overall layout (L=%d)", L);
+  if ((R && R == R_src) || (Z && Z == Z_src) || (stats && stats == S_src))
+    return fail(HQ_E_INVALID, "a destination buffer is its source");
+  hipStream_t s = (hipStream_t)stream;
+  if (flags) HQ_CHECK_HIP(hipMemsetAsync(flags, 0, sizeof(int), s));
+  // groups of 4 rows: the selected rows, then the pad rows of the copies (z16_rows is a multiple of 16)
+  const int64_t groups = ((Z16 || Zov16) ? z16_rows(M) : M + 3) / 4;
+  if (groups == 0) return HQ_OK;
+  // one wave per group, dispatched by the hardware (a grid-stride loop only past 2^22 groups)
+  hipLaunchKernelGGL(k_seg_gather, dim3((unsigned)(groups < (1 << 22) ? groups : (1 << 22))), dim3(64), 0, s, src_row,
+                     M, N_src, si, R_src, Z_src, S_src, R, Z, stats, reinterpret_cast<_Float16*>(Z16), S32, o,
+                     reinterpret_cast<_Float16*>(Zov16), Sov32, flags, groups);
+  HQ_CHECK_LAUNCH();
+  return HQ_OK;
+}
+
+int hq_seg_replace(const double* idx, int64_t M, const int64_t* rows, int L, int src_f32, const uint8_t* row_f32,
+                   int64_t N, double* Z, double* stats, void* Z16, float* S32, void* Zov16, float* Sov32, int* flags,
+                   hq_stream_t stream) {
+  if (L <= 0 || M < 0 || N < 0 || M > N) return fail(HQ_E_INVALID, "bad shape N=%lld M=%lld L=%d", (long long)N, (long long)M, L);
+  if (L > 4096) return fail(HQ_E_UNSUPPORTED, "L=%d (<= 4096)", L);
+  if (M == 0) return HQ_OK;
+  if (!idx || !rows || !Z || !stats) return fail(HQ_E_INVALID, "null buffer");
+  if ((Z16 == nullptr) != (S32 == nullptr) || (Zov16 == nullptr) != (Sov32 == nullptr))
+    return fail(HQ_E_INVALID, "a split copy needs both of its buffers");
+  if (flags && !S32) return fail(HQ_E_INVALID, "the flagged-row list needs the level-0 copies");
+  if (N >= 0x7FFFFFFF) return fail(HQ_E_UNSUPPORTED, "N=%lld rows (int32 row ids)", (long long)N);
+  SegInfo si;
+  seg_info(L, si);
+  if (si.nseg == 0) return fail(HQ_E_INVALID, "no level structure for L=%d", L);
+  if (Z16 && si.plen[0] > 32) return fail(HQ_E_INVALID, "level-0 copies with a level-0 segment of %d values", si.plen[0]);
+  OvLayout o = {};
+  if (Zov16 && !ov_layout(L, o)) return fail(HQ_E_INVALID, "overall copies without a split overall layout (L=%d)", L);
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((unsigned)(M < 65536 ? M : 65536));
+  if (seg_small(si) && si.nseg <= 8 && opt(OPT_PREP_COOP, 1) != 0) {
+    hipLaunchKernelGGL(k_seg_replace<true>, grid, dim3(64), (size_t)8 * si.L, s, idx, M, rows, N, si, src_f32 ? 1 : 0,
+                       row_f32, Z, stats, reinterpret_cast<_Float16*>(Z16), S32, o, reinterpret_cast<_Float16*>(Zov16),
+                       Sov32);
+  } else {
+    hipLaunchKernelGGL(k_seg_replace<false>, grid, dim3(64), (size_t)8 * si.L, s, idx, M, rows, N, si, src_f32 ? 1 : 0,
+                       row_f32, Z, stats, reinterpret_cast<_Float16*>(Z16), S32, o, reinterpret_cast<_Float16*>(Zov16),
+                       Sov32);
+  }
+  HQ_CHECK_LAUNCH();
+  if (flags) {  // a replaced row may enter or leave the list: listed again from the N rows' flag words
+    HQ_CHECK_HIP(hipMemsetAsync(flags, 0, sizeof(int), s));
+    const int64_t fb = (N + 255) / 256;
+    hipLaunchKernelGGL(k_flag_rows, dim3((unsigned)(fb < 4096 ? fb : 4096)), dim3(256), 0, s, S32, N, flags + 1, flags);
+    HQ_CHECK_LAUNCH();
+  }
   return HQ_OK;
 }
 

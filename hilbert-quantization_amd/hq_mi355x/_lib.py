@@ -93,6 +93,8 @@ SIGNATURES = {
     "hq_seg_packov_info": (_i, [_i, _p, _p, _p, _p]),
     "hq_seg_packov_split": (_i, [_p, _p, _i64, _i, _p, _p, _p]),
     "hq_seg_append": (_i, [_p, _i64, _i, _i, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "hq_seg_gather": (_i, [_p, _i64, _i64, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "hq_seg_replace": (_i, [_p, _i64, _p, _i, _i, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p]),
     "hq_scanov_workspace_size": (_sz, [_i, _i64, _i]),
     "hq_scanov_topk_split": (_i, [_p, _p, _p, _p, _i, _p, _p, _p, _p, _i64, _i, _i, _d, _i, _i64, _p, _sz, _p, _p,
                                   _p]),

@@ -29,11 +29,13 @@ class HilbertQuantizer:
     """api.py:27-565 drop-in: HilbertQuantizer(config=None, use_precomputed_indexing=True).
 
     The keyword-only arguments override single config fields (similarity_threshold, max_results,
-    compression_quality, min_efficiency_ratio) without building a SystemConfig."""
+    compression_quality, min_efficiency_ratio) without building a SystemConfig; shrink_resident is the search
+    engine's switch of that name (off by default: see remove_model_from_registry)."""
 
     def __init__(self, config: Optional[SystemConfig] = None, use_precomputed_indexing: bool = True, *,
                  similarity_threshold: Optional[float] = None, max_results: Optional[int] = None,
-                 compression_quality: Optional[float] = None, min_efficiency_ratio: Optional[float] = None):
+                 compression_quality: Optional[float] = None, min_efficiency_ratio: Optional[float] = None,
+                 shrink_resident: bool = False):
         self.config = config or create_default_config()
         if similarity_threshold is not None:
             self.config.search.similarity_threshold = similarity_threshold
@@ -44,6 +46,8 @@ class HilbertQuantizer:
         if min_efficiency_ratio is not None:
             self.config.quantization.min_efficiency_ratio = min_efficiency_ratio
         self.use_precomputed_indexing = use_precomputed_indexing
+        # registry searches after a removal shrink the resident corpus instead of rebuilding it (the engine's switch)
+        self.shrink_resident = bool(shrink_resident)
         self._pipeline: Optional[QuantizationPipeline] = None
         self._engine: Optional[ProgressiveSimilaritySearchEngine] = None
         self._precomputed_indexer: Optional[PrecomputedHilbertIndexer] = None
@@ -80,6 +84,7 @@ class HilbertQuantizer:
     def search_engine(self) -> ProgressiveSimilaritySearchEngine:
         if self._engine is None:
             self._engine = ProgressiveSimilaritySearchEngine(self.similarity_threshold, self.max_results * 2)
+            self._engine.shrink_resident = self.shrink_resident
         return self._engine
 
     @property
@@ -196,7 +201,9 @@ class HilbertQuantizer:
 
     def remove_model_from_registry(self, model_id: str) -> bool:
         """api.py:310-325: drop the first model of that name; False when there is none.  A model removed before
-        the registry's end breaks the resident corpus's prefix, so the next registry search rebuilds it."""
+        the registry's end breaks the resident corpus's prefix, so the next registry search rebuilds it — or,
+        with shrink_resident=True, drops that row from the resident corpus (IndexCorpus.remove: one gather
+        launch) and appends the registry's new tail."""
         for i, model in enumerate(self._model_registry):
             if model.metadata.model_name == model_id:
                 del self._model_registry[i]

@@ -155,7 +155,12 @@ class IndexCorpus:
     searches are readers that take the rows past N for pad rows, so the caller must not append or reserve
     while another thread is searching the same corpus, nor while a search queued on another stream may still
     be running.  Submitted batches not yet finished are counted, and a writer called with that count non-zero
-    raises RuntimeError.  A search issued after `append` returns sees the new rows, on any stream."""
+    raises RuntimeError.  A search issued after `append` returns sees the new rows, on any stream.
+
+    Mutable: `remove` drops rows (the survivors, renumbered, gathered into a second set of buffers by one
+    hq_seg_gather launch), `replace` overwrites rows in place (hq_seg_replace) and `select` cuts a new corpus
+    out of this one.  `remove` and `replace` are writers like `append`; `select` only reads.  Each leaves
+    exactly the corpus a fresh build of the resulting rows would be."""
 
     # bound on |approximate - exact| score: the level-0 scan contracts in split f16 on the matrix cores
     # (|dscore| <= ~5.5e-6, hq_mi355x.h), the other scans in f64 (< 1e-13)
@@ -237,6 +242,103 @@ class IndexCorpus:
         self.prep, self.N = prep, prep.N
         self._mark_ready()
         return self.N
+
+    def _local_rows(self, rows, what: str) -> np.ndarray:
+        """Local row numbers (sequence, NumPy array or device tensor) as a host int64 array, every one in
+        [0, N): IndexError otherwise (raised on the host, before any launch)."""
+        a = to_np(rows) if is_tensor(rows) else np.asarray(rows)
+        a = a.reshape(-1)
+        if a.size and a.dtype.kind not in "iu":
+            raise TypeError(f"IndexCorpus.{what}: row numbers must be integers")
+        a = a.astype(np.int64)
+        if a.size and (a.min() < 0 or a.max() >= self.N):
+            bad = int(a.min()) if a.min() < 0 else int(a.max())
+            raise IndexError(f"IndexCorpus.{what}: row {bad} outside [0, {self.N})")
+        return a
+
+    def remove(self, rows) -> int:
+        """Drop the local rows `rows` (sequence, NumPy array or device tensor; duplicates tolerated).  The
+        survivors keep their order and are renumbered consecutively (global id = id_base + new position), exactly
+        a fresh IndexCorpus of the surviving rows: one hq_seg_gather launch into a second set of buffers of the
+        same capacity.  IndexError for a row outside [0, N) and ValueError for removing every row, both before
+        any launch.  Statistics and adaptive list lengths are kept.  A writer: see the class docstring.
+        Returns the new N."""
+        drop = self._local_rows(rows, "remove")
+        keep = np.ones(self.N, dtype=bool)
+        keep[drop] = False
+        sel = np.flatnonzero(keep)
+        if sel.size == 0:
+            raise ValueError("IndexCorpus.remove: no row would be left")
+        self._writer("remove")
+        if sel.size == self.N:
+            return self.N
+        prep = K.seg_gather(self.prep, sel, checked=True)
+        # a fresh build's test (the constructor's); removing rows can only clear it (one host sync, float32 only)
+        if self.dense_only:
+            self.dense_only = bool(prep.unsafe_rows().any()) if prep.f32 else False
+        self.prep, self.N = prep, prep.N
+        self._mark_ready()
+        return self.N
+
+    def replace(self, rows, indices, row_f32=None) -> int:
+        """Overwrite the distinct local rows `rows` with `indices` [len(rows), L] in place (float32 input, or
+        row_f32 flags, as in the constructor); ids do not change.  One hq_seg_replace call; exactly a fresh
+        IndexCorpus of the updated rows.  IndexError for a row outside [0, N), ValueError for repeated rows or a
+        wrong shape, before any launch.  A writer: see the class docstring.  Returns N."""
+        t = torch()
+        sel = self._local_rows(rows, "replace")
+        if np.unique(sel).size != sel.size:
+            raise ValueError("IndexCorpus.replace: repeated row numbers")
+        f32 = _is_f32(indices)
+        if not is_tensor(indices):
+            indices = np.asarray(indices)
+        if indices.ndim == 1:
+            indices = indices.reshape(1, -1)
+        if indices.ndim != 2 or int(indices.shape[1]) != self.L or int(indices.shape[0]) != sel.size:
+            raise ValueError(f"IndexCorpus.replace expects [{sel.size}, {self.L}] index vectors")
+        M = sel.size
+        flags = None if f32 or row_f32 is None else np.asarray(row_f32, dtype=bool).reshape(-1)
+        if flags is not None and flags.size != M:
+            raise ValueError("row_f32 needs one flag per row")
+        self._writer("replace")
+        if M == 0:
+            return self.N
+        x = _f64(indices)
+        new32 = np.full(M, f32, dtype=bool) if flags is None else flags
+        if self.L > 4096:
+            # hq_seg_replace takes L <= 4096: rebuild from the updated raw rows (aux bit 1: float32 source)
+            all_flags = to_np((self.prep.S[:, 0, 3].to(t.int64) & 1).bool()) if self.prep.f32 \
+                else np.zeros(self.N, dtype=bool)
+            all_flags = all_flags.copy()
+            all_flags[sel] = new32
+            R = self.prep.R.clone()
+            R.index_copy_(0, to_dev(sel), x)
+            prep = K.seg_prepare(R, row_f32=all_flags if all_flags.any() else None)
+            prep = K.flag_rows(K.packov(K.pack0(prep)))
+        else:
+            prep = K.seg_replace(self.prep, sel, x, src_f32=f32, row_f32=flags, checked=True)
+        # as a fresh build: float32 rows outside the scans' model (one host sync, float32 rows only)
+        if new32.any() or self.dense_only:
+            self.dense_only = bool(prep.unsafe_rows().any()) if prep.f32 else False
+        self.prep = prep
+        self._mark_ready()
+        return self.N
+
+    def select(self, rows, id_base: int = 0) -> "IndexCorpus":
+        """A new, independent corpus of the local rows `rows`, in that order (repeats allowed; row i of the result
+        has the global id id_base + i): one hq_seg_gather launch, exactly IndexCorpus(rows' vectors, id_base).
+        This corpus is only read (a search, not a writer).  IndexError for a row outside [0, N)."""
+        sel = self._local_rows(rows, "select")
+        if K.stream() != self._built_on:
+            torch().cuda.current_stream().wait_event(self._ready)
+        prep = K.seg_gather(self.prep, sel, cap=max(1, sel.size), checked=True)
+        c = object.__new__(IndexCorpus)
+        c.N, c.L, c.id_base = prep.N, self.L, int(id_base)
+        c.prep, c.nseg = prep, prep.nseg
+        c.dense_only = bool(prep.unsafe_rows().any()) if prep.f32 and prep.N else False
+        c._pending = 0
+        c._mark_ready()
+        return c
 
     def _warm_redo(self, x):
         """Once per process, with the first corpus built: one 1-query progressive batch whose list is marked
@@ -801,8 +903,35 @@ class IndexCorpus:
         return ids, sc
 
 
+def _pool_diff(cached, arrays) -> Optional[Tuple[List[int], int]]:
+    """How a pool `arrays` continues the cached pool `cached` after removals: (the positions in `cached` that
+    survive, the index in `arrays` where the new tail starts), when `arrays` is the surviving cached entries —
+    matched by identity, in order — followed by entries that are new.  None when it is not: an entry before
+    the tail that the cached pool does not hold at or after the running position (a reordering, a foreign
+    array in the middle: the would-be tail then holds a dropped cached entry), or nothing surviving.  One
+    two-pointer pass over `cached`, O(len(cached) + len(arrays))."""
+    kept: List[int] = []
+    j, n = 0, len(arrays)
+    for i, a in enumerate(cached):
+        if j < n and arrays[j] is a:
+            kept.append(i)
+            j += 1
+    if not kept:
+        return None
+    if j < n and len(kept) < len(cached):
+        keep = set(kept)
+        dropped = {id(a) for i, a in enumerate(cached) if i not in keep}
+        if any(id(a) in dropped for a in arrays[j:]):
+            return None
+    return kept, j
+
+
 class ProgressiveSimilaritySearchEngine(*_bases("interfaces", "SimilaritySearchEngine")):
     """Drop-in for core/search_engine.py:23 (interfaces.py:191-225 SimilaritySearchEngine)."""
+
+    # True: a pool that lost entries of the cached one (a registry after remove_model_from_registry) shrinks
+    # the resident corpus (IndexCorpus.remove, then an append of the new tail) instead of rebuilding it
+    shrink_resident = False
 
     def __init__(self, similarity_threshold: float = 0.1, max_candidates_per_level: int = 100):
         self.similarity_threshold = similarity_threshold
@@ -810,12 +939,19 @@ class ProgressiveSimilaritySearchEngine(*_bases("interfaces", "SimilaritySearchE
         # [index arrays of the last uniform pool, their resident IndexCorpus, searches using it right now]
         self._pool_cache = None
         self._pool_stats = {"builds": 0, "appends": 0}
+        self._pool_shrinks = 0
 
     @property
     def pool_stats(self) -> Dict[str, int]:
         """How the resident pool corpus came about so far: full builds, and appends of a pool's new tail."""
         with _lock(self):
             return dict(self._pool_stats)
+
+    @property
+    def pool_shrinks(self) -> int:
+        """Removals applied to the resident pool corpus in place of a rebuild (shrink_resident)."""
+        with _lock(self):
+            return self._pool_shrinks
 
     # ---- structure -----------------------------------------------------------------------------
     def _parse_index_structure(self, indices, total_space: int) -> List[LevelConfig]:
@@ -862,6 +998,23 @@ class ProgressiveSimilaritySearchEngine(*_bases("interfaces", "SimilaritySearchE
                     hit[0].extend(tail)
                     hit[2] += 1
                     self._pool_stats["appends"] += 1
+                    return hit[1]
+            elif hit is not None and self.shrink_resident and hit[2] == 0 and hit[1]._pending == 0:
+                diff = _pool_diff(hit[0], arrays)
+                if diff is not None:
+                    kept, t0 = diff
+                    keep = np.zeros(n, dtype=bool)
+                    keep[kept] = True
+                    hit[1].remove(np.flatnonzero(~keep))
+                    hit[0][:] = [hit[0][k] for k in kept]
+                    self._pool_shrinks += 1
+                    tail = arrays[t0:]
+                    if tail:
+                        flags = np.array([_is_f32(r) for r in tail], dtype=bool)
+                        hit[1].append(np.stack([np.asarray(r, dtype=np.float64) for r in tail]), row_f32=flags)
+                        hit[0].extend(tail)
+                        self._pool_stats["appends"] += 1
+                    hit[2] += 1
                     return hit[1]
             corpus = self._corpus(arrays)
             self._pool_cache = [arrays, corpus, 1]

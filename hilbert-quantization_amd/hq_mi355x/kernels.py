@@ -507,6 +507,106 @@ def seg_append(p: Prepared, rows, src_f32: bool = False, row_f32=None, exc=None)
     return q
 
 
+def _row_ids(rows, n: int, dev, what: str, checked: bool = False):
+    """Row numbers (sequence, NumPy array or tensor) as a contiguous device int64 [M]; every value must lie in
+    [0, n): IndexError otherwise, before anything is launched (a device tensor costs one host sync; checked:
+    the caller has done it)."""
+    t = torch()
+    if isinstance(rows, t.Tensor):
+        sel = _contig(rows.reshape(-1).to(device=dev, dtype=t.int64))
+        if not checked and sel.numel():
+            lo, hi = (int(v) for v in sel.aminmax())
+            if lo < 0 or hi >= n:
+                raise IndexError(f"{what}: row {lo if lo < 0 else hi} outside [0, {n})")
+        return sel
+    a = np.asarray(rows).reshape(-1)
+    if a.size and a.dtype.kind not in "iu":
+        raise TypeError(f"{what}: row numbers must be integers")
+    a = a.astype(np.int64)
+    if not checked and a.size and (a.min() < 0 or a.max() >= n):
+        raise IndexError(f"{what}: row {int(a.min()) if a.min() < 0 else int(a.max())} outside [0, {n})")
+    return t.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+
+def _f32_state(p: Prepared, S):
+    """(f32, all32) of the rows whose statistics are S, taken from a corpus p: what a fresh build of those rows
+    reports.  An all-float32 or all-float64 corpus needs no look; a mixed one reads aux bit 1 of S[:, 0, 3]
+    (one host sync)."""
+    if not p.f32:
+        return False, False
+    if p.all32:
+        return True, True
+    if S.shape[0] == 0:
+        return False, False
+    t = torch()
+    bits = (S[:, 0, 3].to(t.int64) & 1).to(t.float64)
+    n32 = int(bits.sum())
+    return n32 > 0, n32 == S.shape[0]
+
+
+def seg_gather(p: Prepared, src_rows, cap: Optional[int] = None, exc=None, checked: bool = False) -> Prepared:
+    """A new Prepared of the rows p[src_rows] (row numbers in [0, p.N), any order, repeats allowed), in a second
+    set of buffers with room for max(cap or p.cap, M) rows: one hq_seg_gather launch copies each row's R / Z / S
+    and writes every split layout p carries (pack0, packov, flag_rows), byte-identical to a fresh build of the
+    selected rows.  p is only read.  IndexError for a row out of range, before the launch."""
+    t = torch()
+    dev = p.Z.device
+    sel = _row_ids(src_rows, p.N, dev, "seg_gather", checked)
+    M = int(sel.numel())
+    cap = max(int(cap) if cap else p.cap, M)
+    Rb = t.empty((cap, p.L), dtype=t.float64, device=dev)
+    Zb = t.empty((cap, p.Lp), dtype=t.float64, device=dev)
+    Sb = t.empty((cap, p.nseg, 4), dtype=t.float64, device=dev)
+    q = Prepared(Rb[:M], Zb[:M], Sb[:M], p.L)
+    q.cap, q.base = cap, (Rb, Zb, Sb)
+    if p.Z16 is not None:
+        q.Z16 = t.empty((_rows16(cap), 64), dtype=t.float16, device=dev)
+        q.S32 = t.empty((_rows4(cap), 4), dtype=t.float32, device=dev)
+    if p.Zov16 is not None:
+        q.Zov16 = t.empty((_rows16(cap), p.Zov16.shape[1]), dtype=t.float16, device=dev)
+        q.Sov32 = t.empty((_rows4(cap) // 4, p.Sov32.shape[1]), dtype=t.float32, device=dev)
+    if p.F0 is not None:
+        q.F0 = t.empty(1 + cap, dtype=t.int32, device=dev)
+    _chk(_L().hq_seg_gather(ptr(sel), M, p.N, p.L, ptr(p.R), ptr(p.Z), ptr(p.S), ptr(Rb), ptr(Zb), ptr(Sb), ptr(q.Z16),
+                            ptr(q.S32), ptr(q.Zov16), ptr(q.Sov32), ptr(q.F0), stream()), exc)
+    q.f32, q.all32 = _f32_state(p, q.S)
+    return q
+
+
+def seg_replace(p: Prepared, rows, new_rows, src_f32: bool = False, row_f32=None, exc=None,
+                checked: bool = False) -> Prepared:
+    """p with the resident rows `rows` (distinct row numbers in [0, p.N)) overwritten in place by `new_rows`
+    [M, L] (src_f32 / row_f32 as seg_prepare): R by index_copy_, then one hq_seg_replace call rewrites those
+    rows' Z / S and split layouts and lists the flagged rows again; byte-identical to a fresh build of the
+    updated rows.  A writer, as seg_append: no scan of p may be running.  Returns a new Prepared over the same
+    buffers (a p built to size is first moved into buffers of its own, once: its R may be the caller's tensor).
+    IndexError for a row out of range, ValueError for a repeated row, before any launch."""
+    t = torch()
+    r2 = _contig((new_rows if new_rows.dim() == 2 else new_rows.view(1, -1)).to(t.float64))
+    M, L = r2.shape
+    if L != p.L:
+        raise ValueError(f"replacement index length {L} != corpus index length {p.L}")
+    sel = _row_ids(rows, p.N, r2.device, "seg_replace", checked)
+    if int(sel.numel()) != M:
+        raise ValueError(f"{int(sel.numel())} row numbers for {M} replacement rows")
+    if not checked and M > 1 and int(t.unique(sel).numel()) != M:
+        raise ValueError("seg_replace: repeated row numbers")
+    rf, any32, all32 = _row_flags(src_f32, row_f32, M, r2.device, all_needs_rows=False)
+    if M == 0:
+        return p
+    if p.base is None:  # built to size: R may be the caller's own tensor (seg_prepare keeps it), so move first
+        p = seg_reserve(p, p.cap)
+    p.R.index_copy_(0, sel, r2)
+    _chk(_L().hq_seg_replace(ptr(r2), M, ptr(sel), L, 1 if src_f32 else 0, ptr(rf), p.N, ptr(p.Z), ptr(p.S), ptr(p.Z16),
+                             ptr(p.S32), ptr(p.Zov16), ptr(p.Sov32), ptr(p.F0), stream()), exc)
+    q = Prepared(p.R, p.Z, p.S, L, p.f32 or any32, all32 and p.all32)
+    q.cap, q.base = p.cap, p.base
+    q.Z16, q.S32, q.Zov16, q.Sov32, q.F0 = p.Z16, p.S32, p.Zov16, p.Sov32, p.F0
+    if q.f32 and not q.all32:  # mixed: float32 rows may all have left, or every float64 row may have
+        q.f32, q.all32 = _f32_state(q, q.S)
+    return q
+
+
 def level_scores(q: Prepared, c: Prepared, level: int, exc=None):
     """Dense EXACT [Q, N] level (>= 0) or overall (level = -1) scores (reference operation order)."""
     t = torch()

@@ -343,6 +343,35 @@ int hq_seg_packov_split(const double* Z, const double* S, int64_t N, int L, void
  *   that reads the corpus (stream order or an event): readers of N0 rows treat [N0, ...) as pad rows.        */
 int hq_seg_append(const double* idx, int64_t M, int L, int src_f32, const uint8_t* row_f32, int64_t N0, double* Z,
                   double* stats, void* Z16, float* S32, void* Zov16, float* Sov32, int* flags, hq_stream_t stream);
+/* hq_seg_gather: select M rows of a resident corpus of N_src rows into a SECOND set of buffers in ONE launch:
+ *   destination row i becomes source row src_row[i] (device int64 [M], every value in [0, N_src): any order,
+ *   repeats allowed; the range is the caller's precondition).  Removing rows is the gather of the survivors.
+ *   R, Z, stats, Z16, S32, Zov16, Sov32 and flags are the bases of the destination buffers, each with room for
+ *   M rows and its padding (round_up(M, 16) + 48 rows of Z16 / Zov16, round_up(M, 4) + 48 rows of S32 / Sov32,
+ *   1 + M ints of flags); no destination may alias a source.  One wave per 4 destination rows copies their raw
+ *   values (R_src and R may both be NULL), Z and stats (nothing is recomputed: they are functions of the row
+ *   alone), then writes their split level-0 copies, split overall copies and flag-list entries from the copy;
+ *   further workgroups write the pad rows after M; flags[0] is cleared on the stream first.  Afterwards every buffer
+ *   equals, byte for byte, what hq_seg_prepare_rows (with the rows' float32 flags), hq_seg_pack0_split,
+ *   hq_seg_packov_split and hq_seg_flag_rows (as a set) write for the M selected rows.  Z16 / S32, Zov16 /
+ *   Sov32 and flags may be NULL as for hq_seg_append.  Any L with a level structure (nothing is recomputed, so
+ *   no L <= 4096 limit); M = 0 writes the pad rows of an empty corpus and flags[0] = 0; M >= 2^31 - 1:
+ *   HQ_E_UNSUPPORTED (int32 row ids).  Order the call after the writers of the source, as a scan.            */
+int hq_seg_gather(const int64_t* src_row, int64_t M, int64_t N_src, int L, const double* R_src, const double* Z_src,
+                  const double* S_src, double* R, double* Z, double* stats, void* Z16, float* S32, void* Zov16,
+                  float* Sov32, int* flags, hq_stream_t stream);
+/* hq_seg_replace: overwrite M resident rows of a corpus of N rows IN PLACE with the rows of idx (f64 [M, L];
+ *   src_f32 / row_f32 [M] as hq_seg_prepare_rows): row rows[i] (device int64 [M], distinct values in [0, N): the
+ *   caller's precondition) takes idx row i.  One launch runs hq_seg_append's per-row steps (Z, stats, split
+ *   level-0 copy, split overall copy) on those rows; every other row and every pad row keeps its bytes.  A
+ *   replaced row may enter or leave the flagged-row list, so flags (when given) is then cleared and listed
+ *   again from the N rows' flag words (hq_seg_flag_rows's kernel) on the same stream.  Afterwards every buffer
+ *   equals, byte for byte, a fresh build of the updated rows (flags as a set).  The raw rows are the caller's
+ *   to update.  NULL pairs as for hq_seg_append; L <= 4096 (else HQ_E_UNSUPPORTED); M = 0 writes nothing.  A
+ *   writer: order it after every scan that reads the corpus.                                                 */
+int hq_seg_replace(const double* idx, int64_t M, const int64_t* rows, int L, int src_f32, const uint8_t* row_f32,
+                   int64_t N, double* Z, double* stats, void* Z16, float* S32, void* Zov16, float* Sov32, int* flags,
+                   hq_stream_t stream);
 size_t hq_scanov_workspace_size(int Q, int64_t N, int k);
 int hq_scanov_topk_split(const void* Zq16, const float* Sq32, const double* Sq, const double* Zq, int Q,
                          const void* Zc16, const float* Sc32, const double* Sc, const double* Zc, int64_t N, int L,
