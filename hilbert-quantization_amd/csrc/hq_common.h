@@ -54,6 +54,7 @@ enum Opt {
   OPT_REFINE_COOP, OPT_PRECOMP_COMPACT, OPT_PREP_COOP, OPT_POOL_SORT_MEM, OPT_REFINE_SMALL,
   OPT_RANK_CT, OPT_RANK_WIN, OPT_RANK_SORT_NT, OPT_RANK_SORT_SMALL,
   OPT_DECODE_NT, OPT_DECODE_GENERIC,
+  OPT_COS_TOPK_HINT,
   OPT_COUNT
 };
 int64_t opt(Opt id, int64_t dflt);

@@ -23,6 +23,11 @@
 // is read from HBM once.  Epilogue: (acc * inv_q * inv_c + 1) / 2, f64 stores.  A/B forms (option
 // cos_kernel): the LDS-DMA kernel k_cos_g3 (ping-pong / lockstep) and the register-staged
 // k_cos_mfma on the row-major layout, and other k_cos_t tiles / prefetch distances / epilogues.
+//
+// Fused top-k (hq_cos_topk): k_cos_t<3, 1, 1, 4> keeps the K loop and selects the best k
+// passing frames of every (query, 384-frame tile) in its epilogue instead of storing scores; k_cos_topk_merge
+// reduces the tiles' sorted lists 64 at a time.  Same accumulators, same epilogue expression, same total order
+// as hq_select_topk on the dense matrix: identical ids, order and score bits, memory O(Q k N / 384).
 #include "hq_common.h"
 
 #include <stdlib.h>
@@ -165,7 +170,163 @@ struct CosArgs {
   int64_t ntiles;
   double* out;  // [Q, N]
   float* outf;  // [Q, N] float32 scores (hq_cos_scores_mfma_f32; k_cos_t EP 3): the reference's precision
+  // hq_cos_topk (k_cos_t EP 4): the best tk_k passing frames of every (query, frame tile), [Q, ntiles, tk_k]
+  double* tk_s;
+  int64_t* tk_id;      // frame rows (no id_base), -1 = empty
+  uint64_t* tk_hint;   // [Q] running threshold keys (cos_key), or NULL
+  double tk_thr;
+  int tk_mode;         // 0 none, 1 >= tk_thr, 2 > tk_thr
+  int tk_k;
 };
+
+// ---- top-k pieces of the fused frame search (hq_cos_topk) ---------------------------------------------
+// The total order of hq_select_topk: score descending, id ascending.
+__device__ __forceinline__ bool cos_better(double s, int64_t id, double s2, int64_t id2) {
+  return s > s2 || (s == s2 && id < id2);
+}
+// order-preserving u64 key of a score (the sign-flip map: (cs + 1) / 2 can be a hair below 0); 0 is below
+// the key of every number, so a zeroed hint is "none"
+__device__ __forceinline__ uint64_t cos_key(double s) {
+  const uint64_t b = (uint64_t)__double_as_longlong(s);
+  return (b >> 63) ? ~b : b | 0x8000000000000000ull;
+}
+// wave arg-max in the total order (id < 0: empty); every lane ends with the same pair
+__device__ __forceinline__ void cos_wave_best(double& bs, int64_t& bi) {
+  for (int o = 1; o < 64; o <<= 1) {
+    const double s2 = __shfl_xor(bs, o, 64);
+    const int64_t i2 = __shfl_xor(bi, o, 64);
+    if (i2 >= 0 && (bi < 0 || cos_better(s2, i2, bs, bi))) { bs = s2; bi = i2; }
+  }
+}
+// The same for the epilogue's (score, column) pairs, without LDS round trips (the per-round critical path of
+// the top-k epilogue): four DPP steps (xor 1, xor 2, half-row mirror, row mirror) leave every 16-lane row
+// with its best pair, four readlanes combine the rows.  The order is total and the columns distinct, so the
+// shape of the reduction does not change the result.
+__device__ __forceinline__ void cos_take(double& bs, int& bi, double s2, int i2) {
+  if (i2 >= 0 && (bi < 0 || s2 > bs || (s2 == bs && i2 < bi))) { bs = s2; bi = i2; }
+}
+template <int CTRL>
+__device__ __forceinline__ void cos_dpp_best(double& bs, int& bi) {
+  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(bs), CTRL, 0xF, 0xF, false);
+  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(bs), CTRL, 0xF, 0xF, false);
+  const int i2 = __builtin_amdgcn_update_dpp(0, bi, CTRL, 0xF, 0xF, false);
+  cos_take(bs, bi, __hiloint2double(hi, lo), i2);
+}
+__device__ __forceinline__ void cos_wave_best(double& bs, int& bi) {
+  cos_dpp_best<0xB1>(bs, bi);
+  cos_dpp_best<0x4E>(bs, bi);
+  cos_dpp_best<0x141>(bs, bi);
+  cos_dpp_best<0x140>(bs, bi);
+  const int lo = __double2loint(bs), hi = __double2hiint(bs), e = bi;
+  bs = __hiloint2double(__builtin_amdgcn_readlane(hi, 0), __builtin_amdgcn_readlane(lo, 0));
+  bi = __builtin_amdgcn_readlane(e, 0);
+#pragma unroll
+  for (int l = 16; l < 64; l += 16)
+    cos_take(bs, bi, __hiloint2double(__builtin_amdgcn_readlane(hi, l), __builtin_amdgcn_readlane(lo, l)),
+             __builtin_amdgcn_readlane(e, l));
+}
+
+// One query of one workgroup tile, one wave: the TN staged scores of row `row` (st: 8 wave slices of
+// 16 x TN / 8 f64, the wide epilogue's staging) are TN / 64 per lane, candidate e = lane + 64 u = frame
+// nt TN + e.  Frames n >= N (the clamped last tile re-reads real rows) and those failing the threshold test
+// are masked; then tk_k arg-max rounds, each pick leaving its lane's set, write (score, frame) to the fixed
+// slab position [q][nt][0 .. tk_k), padded with -inf / -1.
+// Running threshold (hint != NULL): hint[q] is the key of some tile's k-th pick, so k passing frames score
+// at or above it; candidates strictly below it leave the set before the first round (they cannot reach the
+// merged top k; ties are kept), the rounds end when the set is empty, and a tile that found all k raises it.
+// Relaxed, no ordering: a stale read is only lower, so the merged result does not depend on timing.
+template <int TN>
+__device__ __forceinline__ void cos_topk_row(const double* __restrict__ st, int row, int64_t q, int64_t nt,
+                                             const CosArgs& a) {
+  constexpr int C = TN / 64, WC = TN / 8;  // candidates per lane, frames per wave slice
+  const int lane = threadIdx.x & 63;
+  const int k = a.tk_k;
+  uint64_t hint = 0;
+  if (a.tk_hint) hint = __hip_atomic_load(a.tk_hint + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  double s[C];
+  unsigned live = 0;
+#pragma unroll
+  for (int u = 0; u < C; ++u) {
+    const int e = lane + 64 * u;
+    const double v = st[(e / WC) * (16 * WC) + row * WC + e % WC];
+    const bool pass = a.tk_mode == 0 || (a.tk_mode == 1 ? v >= a.tk_thr : v > a.tk_thr);
+    s[u] = v;
+    if (nt * TN + e < a.N && pass && cos_key(v) >= hint) live |= 1u << u;  // strictly below the hint: out
+  }
+  double* os = a.tk_s + (q * a.ntiles + nt) * k;
+  int64_t* oi = a.tk_id + (q * a.ntiles + nt) * k;
+  int j = 0;
+  double bs = 0.0;
+  for (; j < k; ++j) {
+    if (__ballot(live != 0) == 0) break;  // nothing left at or above the hint: no reduction for this round
+    bs = 0.0;
+    int be = -1;
+#pragma unroll
+    for (int u = 0; u < C; ++u)  // e ascends with u: strict > keeps the lowest frame of a tie
+      if (((live >> u) & 1u) && (be < 0 || s[u] > bs)) { bs = s[u]; be = lane + 64 * u; }
+    cos_wave_best(bs, be);
+    if (lane == 0) {
+      os[j] = bs;
+      oi[j] = nt * TN + be;
+    }
+    if ((be & 63) == lane) live &= ~(1u << (be >> 6));
+  }
+  if (j == k) {
+    if (a.tk_hint && lane == 0)
+      __hip_atomic_fetch_max(a.tk_hint + q, cos_key(bs), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  } else {
+    for (int jj = j + lane; jj < k; jj += 64) {
+      os[jj] = -__builtin_huge_val();
+      oi[jj] = -1;
+    }
+  }
+}
+
+// Merge stage of hq_cos_topk: list g of query q (out) = the best k of lists [64 g, 64 g + 64) of the P the
+// previous stage left (each sorted in the total order, -1 padded).  One wave per output list, lane l walks
+// list 64 g + l: its head is the lane's candidate, the wave arg-max takes the best head, that lane steps to
+// its next entry.  ids leave with id_add added (id_base in the last stage, 0 before it).
+__global__ __launch_bounds__(64) void k_cos_topk_merge(int Q, int64_t P, int64_t P2, int k, int64_t id_add,
+                                                       const double* __restrict__ i_s,
+                                                       const int64_t* __restrict__ i_id, double* __restrict__ o_s,
+                                                       int64_t* __restrict__ o_id) {
+  const int lane = threadIdx.x;
+  for (int64_t t = blockIdx.x; t < (int64_t)Q * P2; t += gridDim.x) {
+    const int64_t q = t / P2, p = (t % P2) * 64 + lane;
+    const double* ls = i_s + (q * P + p) * k;
+    const int64_t* li = i_id + (q * P + p) * k;
+    int cur = 0;
+    double hs = 0.0;
+    int64_t hid = -1;
+    if (p < P) {
+      hid = li[0];
+      if (hid >= 0) hs = ls[0];
+    }
+    double* os = o_s + t * k;
+    int64_t* oi = o_id + t * k;
+    for (int j = 0; j < k; ++j) {
+      double bs = hs;
+      int64_t bi = hid;
+      cos_wave_best(bs, bi);
+      if (bi < 0) {
+        for (int jj = j + lane; jj < k; jj += 64) {
+          os[jj] = -__builtin_huge_val();
+          oi[jj] = -1;
+        }
+        break;
+      }
+      if (lane == 0) {
+        os[j] = bs;
+        oi[j] = bi + id_add;
+      }
+      if (hid == bi) {  // ids are distinct: exactly one lane
+        ++cur;
+        hid = cur < k ? li[cur] : -1;
+        if (hid >= 0) hs = ls[cur];
+      }
+    }
+  }
+}
 
 // Register-staged baseline.  TQ = query rows per workgroup tile; frames per tile kCosT = 128.  LDS per
 // buffer: (2 TQ + 2 * 128) rows of 80 B.
@@ -659,6 +820,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
           if (v == -1.0) a.out[0] = v;
         } else if constexpr (EP == 3) {  // float32 scores: the f64 value rounded once
           if (q < a.Q && n < a.N) __builtin_nontemporal_store((float)v, a.outf + q * a.N + n);
+        } else if constexpr (EP == 4) {  // top-k: every value is staged, rows and columns are masked below
+          stage[(4 * (lane >> 4) + r) * 16 * FT + 16 * j + (lane & 15)] = v;
         } else if (wide) {
           stage[(4 * (lane >> 4) + r) * 16 * FT + 16 * j + (lane & 15)] = v;
         } else if (q < a.Q && n < a.N) {
@@ -680,6 +843,19 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
           else if (n < a.N) __builtin_nontemporal_store(v2.x, a.out + q * a.N + n);
         }
       }
+    }
+    if constexpr (EP == 4) {
+      // EP 4 (hq_cos_topk): the 16 queries of the row block against the tile's TN frames are now staged in
+      // the eight wave slices; wave w selects for queries 2 w and 2 w + 1 (padded query rows write nothing).
+      // Every wave of the workgroup reaches both barriers of every row block.
+      __syncthreads();
+#pragma unroll 1
+      for (int h = 0; h < 2; ++h) {
+        const int row = 2 * wv + h;
+        const int64_t q = q0 + 16 * i + row;
+        if (q < a.Q) cos_topk_row<TN>(reinterpret_cast<const double*>(smem), row, q, nt, a);
+      }
+      __syncthreads();  // the next row block overwrites the stage
     }
   }
 }
@@ -822,6 +998,82 @@ int hq_cos_scores_mfma(const void* A16, const double* inv_a, int Q, const void* 
   if (ek == 95) return launch_t<3, 1, 1, 0, 5>(a, (hipStream_t)stream);
 #endif
   return launch_t<3, 1, 1>(a, (hipStream_t)stream);
+}
+
+// ---- fused top-k ---------------------------------------------------------------------------------------
+// Workspace of hq_cos_topk: [Q] hint keys, the stage-1 slab [Q, P, k] (f64 scores, i64 frames; P = frame
+// tiles of 384) and two merge buffers [Q, ceil(P / 64), k], [Q, ceil(P / 4096), k]; every piece 256-aligned.
+static int64_t cos_topk_tiles(int64_t N) { return (hq_cos_padded_rows(N) + 383) / 384; }
+static size_t cos_topk_al(size_t b) { return (b + 255) & ~(size_t)255; }
+
+size_t hq_cos_topk_workspace_size(int Q, int64_t N, int k) {
+  if (Q <= 0 || N <= 0 || k <= 0) return 0;
+  const size_t P = (size_t)cos_topk_tiles(N), P1 = (P + 63) / 64, P2 = (P1 + 63) / 64;
+  return cos_topk_al((size_t)Q * 8) + 2 * cos_topk_al((size_t)Q * P * k * 8) + 2 * cos_topk_al((size_t)Q * P1 * k * 8) +
+         2 * cos_topk_al((size_t)Q * P2 * k * 8);
+}
+
+int hq_cos_topk(const void* A16, const double* inv_a, int Q, const void* B16, const double* inv_b, int64_t N, int K,
+                int k, double threshold, int thr_mode, int64_t id_base, void* workspace, size_t workspace_bytes,
+                double* out_score, int64_t* out_id, hq_stream_t stream) {
+  if (Q < 0 || N < 0 || K <= 0 || k < 1) return fail(HQ_E_INVALID, "bad shape Q=%d N=%lld K=%d k=%d", Q, (long long)N, K, k);
+  if (Q == 0 || N == 0) return HQ_OK;
+  if (k > 64) return fail(HQ_E_UNSUPPORTED, "k=%d: the fused frame top-k keeps lists of at most 64", k);
+  const int64_t ek = opt(OPT_COS_KERNEL, 0);
+  if (ek >= 1 && ek <= 3)
+    return fail(HQ_E_UNSUPPORTED, "cos_kernel=%lld prepares the row-major layout; the fused frame top-k needs the tiled one",
+                (long long)ek);
+  if (!A16 || !inv_a || !B16 || !inv_b || !workspace || !out_score || !out_id) return fail(HQ_E_INVALID, "null buffer");
+  if (workspace_bytes < hq_cos_topk_workspace_size(Q, N, k)) return fail(HQ_E_INVALID, "workspace too small");
+  const hipStream_t s = (hipStream_t)stream;
+  const int64_t P = cos_topk_tiles(N);
+  uint8_t* w = reinterpret_cast<uint8_t*>(workspace);
+  auto take = [&](size_t bytes) { uint8_t* p = w; w += cos_topk_al(bytes); return p; };
+  uint64_t* hint = reinterpret_cast<uint64_t*>(take((size_t)Q * 8));
+  double* bs[3];
+  int64_t* bi[3];
+  int64_t cap = P;  // lists per query a buffer holds: P, ceil(P / 64), ceil(P / 4096)
+  for (int i = 0; i < 3; ++i) {
+    bs[i] = reinterpret_cast<double*>(take((size_t)Q * cap * k * 8));
+    bi[i] = reinterpret_cast<int64_t*>(take((size_t)Q * cap * k * 8));
+    cap = (cap + 63) / 64;
+  }
+  CosArgs a;
+  a.A = reinterpret_cast<const _Float16*>(A16);
+  a.B = reinterpret_cast<const _Float16*>(B16);
+  a.ia = inv_a;
+  a.ib = inv_b;
+  a.Q = Q;
+  a.N = N;
+  a.Kp = hq_cos_padded_k(K);
+  a.ntiles = hq_cos_padded_rows(N) / kCosT;
+  a.out = nullptr;
+  a.outf = nullptr;
+  a.tk_s = bs[0];
+  a.tk_id = bi[0];
+  a.tk_hint = opt(OPT_COS_TOPK_HINT, 1) ? hint : nullptr;
+  a.tk_thr = threshold;
+  a.tk_mode = thr_mode;
+  a.tk_k = k;
+  if (a.tk_hint) HQ_CHECK_HIP(hipMemsetAsync(hint, 0, (size_t)Q * 8, s));
+  const int rc = launch_t<3, 1, 1, 4>(a, s);  // the default kernel's K loop, top-k epilogue
+  if (rc != HQ_OK) return rc;
+  // merge 64 lists at a time until one is left: slab -> buffer 1 -> buffer 2 -> buffer 1 ...
+  int64_t Pc = P;
+  int cur = 0;
+  for (;;) {
+    const int64_t P2 = (Pc + 63) / 64;
+    const bool last = P2 == 1;
+    const int nxt = cur == 1 ? 2 : 1;
+    const int64_t g = (int64_t)Q * P2 < 65536 ? (int64_t)Q * P2 : 65536;
+    hipLaunchKernelGGL(k_cos_topk_merge, dim3((unsigned)g), dim3(64), 0, s, Q, Pc, P2, k, last ? id_base : (int64_t)0,
+                       (const double*)bs[cur], (const int64_t*)bi[cur], last ? out_score : bs[nxt], last ? out_id : bi[nxt]);
+    HQ_CHECK_LAUNCH();
+    if (last) break;
+    Pc = P2;
+    cur = nxt;
+  }
+  return HQ_OK;
 }
 
 }  // extern "C"

@@ -43,7 +43,8 @@ static const char* const kOptNames[OPT_COUNT] = {
     "precomp_ws", "precomp_leaf_rot", "precomp_order", "precomp_g2reg",
     "refine_coop", "precomp_compact", "prep_coop", "pool_sort_mem", "refine_small",
     "rank_ct", "rank_win", "rank_sort_nt", "rank_sort_small",
-    "decode_nt", "decode_generic"};
+    "decode_nt", "decode_generic",
+    "cos_topk_hint"};
 static int64_t g_opt_val[OPT_COUNT];
 static bool g_opt_set[OPT_COUNT];
 

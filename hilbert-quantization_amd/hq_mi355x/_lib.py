@@ -119,6 +119,8 @@ SIGNATURES = {
     "hq_cos_prepare": (_i, [_p, _i64, _i64, _i, _p, _p, _p]),
     "hq_cos_scores_mfma": (_i, [_p, _p, _i, _p, _p, _i64, _i, _p, _p]),
     "hq_cos_scores_mfma_f32": (_i, [_p, _p, _i, _p, _p, _i64, _i, _p, _p]),
+    "hq_cos_topk_workspace_size": (_sz, [_i, _i64, _i]),
+    "hq_cos_topk": (_i, [_p, _p, _i, _p, _p, _i64, _i, _i, _d, _i, _i64, _p, _sz, _p, _p, _p]),
 }
 
 _lock = threading.Lock()

@@ -1021,6 +1021,55 @@ def cosine_scores_mfma(q: CosRows, c: CosRows, exc=None, f32: bool = False):
     return out
 
 
+def _cos_query_block(q: CosRows, q0: int, q1: int) -> CosRows:
+    """Prepared queries [q0, q1), q0 a multiple of 16: query tile t starts at X16[16 t] (1 KiB fragments,
+    tile-major), so a block is a pointer offset into the prepared rows."""
+    return q if (q0 == 0 and q1 == q.N) else CosRows(q.X16[q0:], q.inv[q0:], q1 - q0, q.K)
+
+
+def cosine_topk(q: CosRows, c: CosRows, k: int, threshold: float = 0.0, thr_mode: int = 0, id_base: int = 0,
+                workspace_limit: int = 256 << 20, exc=None):
+    """The k nearest prepared frames of every prepared query -> (scores [Q, k] f64, ids [Q, k] i64), equal to
+    select_topk(cosine_scores_mfma(q, c), k, threshold, thr_mode, id_base) in ids, order and score bits,
+    without the [Q, N] matrix (hq_cos_topk: the selection runs in the GEMM's epilogue).  The workspace is
+    about 16 Q k N / 384 bytes; above workspace_limit the queries run in blocks of a multiple of 128.
+    k > 64 or k > N: the dense scores and select_topk, in query blocks under the same limit."""
+    t = torch()
+    if q.K != c.K:
+        raise ValueError(f"query length {q.K} != frame length {c.K}")
+    k, Q, N = int(k), q.N, c.N
+    if k < 1:
+        raise ValueError(f"k = {k}")
+    dev = q.X16.device
+    os_ = t.full((Q, k), float("-inf"), dtype=t.float64, device=dev)
+    oi = t.full((Q, k), -1, dtype=t.int64, device=dev)
+    if Q == 0 or N == 0:
+        return os_, oi
+    limit = max(int(workspace_limit), 1)
+    if k > 64 or k > N:
+        per = max(128, limit // (8 * N) // 128 * 128)
+        for q0 in range(0, Q, per):
+            q1 = min(Q, q0 + per)
+            s, i, _, _ = select_topk(cosine_scores_mfma(_cos_query_block(q, q0, q1), c, exc), k, threshold, thr_mode,
+                                     id_base, exc)
+            os_[q0:q1], oi[q0:q1] = s, i
+        return os_, oi
+    size = _L().hq_cos_topk_workspace_size
+    per = Q
+    if int(size(Q, N, k)) > limit:
+        per = max(128, limit // max(int(size(128, N, k)), 1) * 128)
+        while per > 128 and int(size(per, N, k)) > limit:
+            per -= 128
+    for q0 in range(0, Q, per):
+        q1 = min(Q, q0 + per)
+        b = _cos_query_block(q, q0, q1)
+        wb = int(size(b.N, N, k))
+        ws = _workspace(wb, dev)
+        _chk(_L().hq_cos_topk(ptr(b.X16), ptr(b.inv), b.N, ptr(c.X16), ptr(c.inv), N, q.K, k, float(threshold),
+                              int(thr_mode), int(id_base), ptr(ws), wb, ptr(os_[q0:q1]), ptr(oi[q0:q1]), stream()), exc)
+    return os_, oi
+
+
 MFMA_COS_MIN_WORK = 1 << 22
 
 

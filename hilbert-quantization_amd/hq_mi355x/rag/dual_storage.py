@@ -169,3 +169,39 @@ class DualStorageCorpus:
         s, ids, _, _ = K.select_topk(sc, max(1, min(int(k), len(self))), 0.0, 0)
         s, ids = to_np(s), to_np(ids)
         return [[(self.metadata[int(i)], float(v)) for v, i in zip(s[r], ids[r]) if i >= 0] for r in range(len(s))]
+
+    def _resident_cos(self):
+        """(prepared original embeddings, their height) of a float32 store whose frames share one detected
+        original height, prepared once; (None, 0) for any other store."""
+        if self._cos is None:
+            t = torch()
+            self._cos = (None, 0)
+            if self.frames.dtype == t.float32 and len(self) > 0:
+                co, ch = self._originals(self.frames)
+                h = int(ch[0])
+                if h > 0 and bool((ch == h).all()):
+                    m = h * int(self.frames.shape[2])  # the rows below the height are zero: leave them out
+                    self._cos = (K.cos_prepare(co.reshape(len(self), -1)[:, :m]), h)
+        return self._cos
+
+    def search_topk(self, query_frames, k: int = 10,
+                    threshold: Optional[float] = None) -> List[List[Tuple[VideoFrameMetadata, float]]]:
+        """search(query_frames, k, "embedding") without the [Q, N] score matrix: a float32 store written by one
+        generator (one original height, shared by the queries) is prepared once, stays resident, and every
+        call is one fused cosine + top-k (hq_cos_topk; scores within 2e-6 of the float64 cosine).  Stores of
+        mixed heights, float64 frames and problems below kernels.MFMA_COS_MIN_WORK take the dense route of
+        search().  threshold: keep only frames scoring >= it."""
+        q = to_dev(query_frames)
+        q = (q.unsqueeze(0) if q.dim() == 2 else q).to(self.frames.dtype)
+        kk = max(1, min(int(k), len(self)))
+        thr, mode = (0.0, 0) if threshold is None else (float(threshold), 1)
+        rows, h = self._resident_cos()
+        s = None
+        if rows is not None and int(q.shape[0]) * len(self) * rows.K >= K.MFMA_COS_MIN_WORK:
+            qo, qh = self._originals(q)
+            if bool((qh == h).all()):
+                s, ids = K.cosine_topk(K.cos_prepare(qo.reshape(qo.shape[0], -1)[:, :rows.K]), rows, kk, thr, mode)
+        if s is None:
+            s, ids, _, _ = K.select_topk(self.scores(q, "embedding"), kk, thr, mode)
+        s, ids = to_np(s), to_np(ids)
+        return [[(self.metadata[int(i)], float(v)) for v, i in zip(s[r], ids[r]) if i >= 0] for r in range(len(s))]

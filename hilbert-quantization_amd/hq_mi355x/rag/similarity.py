@@ -1,8 +1,8 @@
 """RAG scoring functions, reference rag/search/engine.py:134-162, 243-287,
 604-714, 1025-1138.
 
-Every score runs on the GPU (hq_cosine_scores / hq_cosine_scores_dt / hq_cos_scores_mfma,
-hq_spatial_locality, hq_detect_heights, hq_threshold_select); the level weights and the progressive
+Every score runs on the GPU (hq_cosine_scores / hq_cosine_scores_dt / hq_cos_scores_mfma, hq_cos_topk for
+rankings of large float32 problems, hq_spatial_locality, hq_detect_heights, hq_threshold_select); the level weights and the progressive
 thresholds are host-side constants computed with the reference's own Python float expressions.  Inputs
 keep their dtype: float64 arrays are scored in float64 (the reference's np.dot / np.linalg.norm run in
 the input dtype), float32 ones from float32 values."""
@@ -30,6 +30,59 @@ def cosine_scores_batch(a, b):
     if a2.dtype == t.float64 or b2.dtype == t.float64:
         return K.cosine_scores_dt(a2.to(t.float64), b2.to(t.float64))
     return K.cosine_scores(a2, b2)
+
+
+def _threshold_mode(threshold):
+    """threshold=None keeps every frame; a number keeps the frames scoring >= it."""
+    return (0.0, 0) if threshold is None else (float(threshold), 1)
+
+
+def cosine_topk_batch(a, b, k: int, threshold=None):
+    """The k best rows of b [N, K] for every row of a [Q, K] by (score desc, row asc) -> device (scores [Q, k]
+    f64, ids [Q, k] i64; -inf / -1 where fewer pass): the ranking select_topk gives on cosine_scores_batch(a, b).
+    Large float32 problems never form the [Q, N] matrix (hq_cos_topk); float64 rows and small problems do."""
+    t = torch()
+    a2, b2 = to_dev(a), to_dev(b)
+    thr, mode = _threshold_mode(threshold)
+    if a2.dtype == t.float32 and b2.dtype == t.float32:
+        ar, br = a2.reshape(a2.shape[0], -1), b2.reshape(b2.shape[0], -1)
+        m = min(int(ar.shape[1]), int(br.shape[1]))  # the reference truncates to the common length
+        if m > 0 and int(ar.shape[0]) * int(br.shape[0]) * m >= K.MFMA_COS_MIN_WORK:
+            return K.cosine_topk(K.cos_prepare(ar[:, :m]), K.cos_prepare(br[:, :m]), int(k), thr, mode)
+    s, ids, _, _ = K.select_topk(cosine_scores_batch(a2, b2), int(k), thr, mode)
+    return s, ids
+
+
+class FrameCosineCorpus:
+    """Float32 frames [N, ...] prepared once for the matrix-core cosine and kept resident (split-f16 operand
+    fragments + inverse norms); search() returns the nearest k frames of every query in one call, with
+    memory O(Q k N / 384) instead of the [Q, N] score matrix."""
+
+    def __init__(self, frames):
+        x = to_dev(frames)
+        if x.dim() < 2:
+            raise ValueError("frames must be [N, ...]")
+        self.shape = tuple(int(d) for d in x.shape[1:])
+        self._rows = K.cos_prepare(x.reshape(x.shape[0], -1))
+
+    @property
+    def N(self) -> int:
+        return self._rows.N
+
+    @property
+    def K(self) -> int:
+        return self._rows.K
+
+    def __len__(self) -> int:
+        return self._rows.N
+
+    def search(self, queries, k: int = 10, threshold=None):
+        """queries [Q, ...] (or one frame) -> device (scores [Q, k] f64, ids [Q, k] i64), (score desc, frame
+        asc), -inf / -1 where fewer than k frames pass `threshold` (None: no test; else score >= threshold)."""
+        q = to_dev(queries)
+        q2 = q.reshape(1, -1) if q.dim() <= len(self.shape) else q.reshape(q.shape[0], -1)
+        thr, mode = _threshold_mode(threshold)
+        return K.cosine_topk(K.cos_prepare(q2), self._rows, int(k), thr, mode)
 
 
 def calculate_embedding_cosine_similarity(embedding1, embedding2) -> float:

@@ -59,7 +59,7 @@ const char* hq_last_error(void);
  * "rank_win" (0: the long-list ranking by the bitonic sort alone, no window ranking), "rank_sort_nt" (512: lists
  * > 512 in 512-thread workgroups), "rank_sort_small" (0: lists <= 128 in the 1024-entry workgroup), "decode_nt"
  * (0: plain instead of non-temporal stores in hq_dequantize_unmap), "decode_generic" (1: its generic kernel
- * for every n).  Options are
+ * for every n), "cos_topk_hint" (0: hq_cos_topk without the running threshold between tiles).  Options are
  * process-wide: set them before launching, not
  * while other host threads launch.  hq_reset_option restores the default; hq_get_option returns 1 when
  * the option is set (value in *value), 0 when it is at its default, HQ_E_INVALID for an unknown name.
@@ -561,6 +561,22 @@ int hq_cos_scores_mfma(const void* A16, const double* inv_a, int Q, const void* 
                        int K, double* out, hq_stream_t stream);
 int hq_cos_scores_mfma_f32(const void* A16, const double* inv_a, int Q, const void* B16, const double* inv_b, int64_t N,
                            int K, float* out, hq_stream_t stream);
+
+/* hq_cos_topk: the nearest k frames of every query without the Q x N score matrix.  Operands as for
+ *   hq_cos_scores_mfma in the default tiled layout (option cos_kernel 1-3: HQ_E_UNSUPPORTED).  out_score /
+ *   out_id [Q, k]: the best k frames among those passing thr_mode (0 none, 1 >= threshold, 2 > threshold), in
+ *   (score descending, id ascending) order, ids = frame + id_base, empty slots -inf / -1.  The scores are the
+ *   float64 values hq_cos_scores_mfma writes for those pairs, bit for bit, and the lists equal
+ *   hq_select_topk_ws of that matrix.  The GEMM's epilogue selects k frames per (query, 384-frame tile) into
+ *   the workspace and merge launches reduce the tiles' lists 64 at a time; option "cos_topk_hint" (default 1)
+ *   lets tiles skip candidates below a k-th score another tile has already published (same result).
+ *   1 <= k <= 64 (larger: HQ_E_UNSUPPORTED).  workspace: hq_cos_topk_workspace_size(Q, N, k) bytes, about
+ *   16 Q k N / 384.                                                                               */
+size_t hq_cos_topk_workspace_size(int Q, int64_t N, int k);
+int hq_cos_topk(const void* A16, const double* inv_a, int Q, const void* B16, const double* inv_b, int64_t N,
+                int K, int k, double threshold, int thr_mode, int64_t id_base,
+                void* workspace, size_t workspace_bytes,
+                double* out_score, int64_t* out_id, hq_stream_t stream);
 
 /* ---- S7: the rest of the RAG scorer (rag/search/engine.py) --------------------------------------
  * hq_cosine_scores_dt: as hq_cosine_scores for float32 (HQ_F32) or float64 (HQ_F64) rows; float64
