@@ -6,7 +6,9 @@
 // to the common length, dot / (|a| |b|), (cos + 1) / 2, 0.0 when a norm is 0 — applied to every
 // (query, stored frame) pair by the RAG search loops (:503-507, :1025-1051).  The reference computes
 // in float32 through BLAS (sdot / snrm2 order), so scores agree within the north star's 1e-5, not bit
-// for bit (DESIGN.md §4.5 has the error budget).
+// for bit (DESIGN.md §4.5 has the error budget; profiles/cos_error_bounds.txt the error measured per row family:
+// up to 3.2e-6 for same-sign rows at K = 16384).  Every finite float32 row gives finite scores, subnormal rows
+// included; a row with a NaN or inf gets inv = 0 and scores 0.0 (include/hq_mi355x.h).
 //
 // Layout (hq_cos_prepare, once per corpus / query batch): every row x is scaled by a power of two s
 // (max |s x| in [0.5, 1)) and split as hi = f16(s x), lo = f16(s x - hi), Kp = K rounded up to 32, stored
@@ -73,14 +75,15 @@ __global__ __launch_bounds__(256) void k_cos_prepare(const float* __restrict__ X
     }
     int e = 0;
     if (amax > 0.0f) frexpf(amax, &e);  // amax = m 2^e, m in [0.5, 1)
-    const float s = ldexpf(1.0f, -e);   // s x in (-1, 1)
+    // s x = ldexpf(x, -e) in (-1, 1): exact for every finite row (s = 2^-e itself overflows float32 for a
+    // subnormal amax, e <= -128)
     for (int k = lane; k < Kp; k += 64) {
-      const float v = k < K ? x[k] * s : 0.0f;
+      const float v = k < K ? ldexpf(x[k], -e) : 0.0f;
       const _Float16 h = (_Float16)v;
       hi[k] = h;
       lo[k] = (_Float16)(v - (float)h);
     }
-    if (lane == 0) inv[r] = ss > 0.0 ? 1.0 / ((double)s * sqrt(ss)) : 0.0;
+    if (lane == 0) inv[r] = ss > 0.0 ? ldexp(1.0 / sqrt(ss), e) : 0.0;
   }
 }
 
@@ -100,7 +103,7 @@ __global__ __launch_bounds__(1024) void k_cos_prepare_tiled(const float* __restr
   // order (same scale and inverse-norm bits), then the waves split the tile's K steps; per K step lane
   // 16 g + j converts row j's values 8 g .. 8 g + 7, so every fragment leaves as one contiguous 1 KiB wave
   // store per plane
-  __shared__ float sc[16];
+  __shared__ int sc[16];  // the rows' scale exponents e (s = 2^-e)
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, j = lane & 15, g = lane >> 4;
   const int KB = Kp / kCosK;
   // blockIdx.y: one of gridDim.y parts of the K steps (small batches: more workgroups per tile, each
@@ -109,9 +112,9 @@ __global__ __launch_bounds__(1024) void k_cos_prepare_tiled(const float* __restr
   const int kb0 = blockIdx.y * per, kb1 = kb0 + per < KB ? kb0 + per : KB;
   for (int64_t t = blockIdx.x; t < rows_out / 16; t += gridDim.x) {
     const int64_t r0 = 16 * t + wv;
-    if (r0 >= N) {  // pad rows: zeros (scale 0), inv 0
+    if (r0 >= N) {  // pad rows: zeros, inv 0
       if (lane == 0) {
-        sc[wv] = 0.0f;
+        sc[wv] = 0;
         if (blockIdx.y == 0) inv[r0] = 0.0;
       }
     } else {
@@ -129,22 +132,21 @@ __global__ __launch_bounds__(1024) void k_cos_prepare_tiled(const float* __restr
       }
       int e = 0;
       if (amax > 0.0f) frexpf(amax, &e);  // amax = m 2^e, m in [0.5, 1)
-      const float s = ldexpf(1.0f, -e);   // s x in (-1, 1)
       if (lane == 0) {
-        sc[wv] = s;
-        if (blockIdx.y == 0) inv[r0] = ss > 0.0 ? 1.0 / ((double)s * sqrt(ss)) : 0.0;
+        sc[wv] = e;
+        if (blockIdx.y == 0) inv[r0] = ss > 0.0 ? ldexp(1.0 / sqrt(ss), e) : 0.0;
       }
     }
     __syncthreads();
     const int64_t r = 16 * t + j;
-    const float my_s = sc[j];
+    const int my_e = sc[j];
     const float* x = X + (r < N ? r : 0) * ld;
     for (int kb = kb0 + wv; kb < kb1; kb += 16) {
       h8 hi, lo;
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
         const int k = kCosK * kb + 8 * g + u;
-        const float v = (r < N && k < K) ? x[k] * my_s : 0.0f;
+        const float v = (r < N && k < K) ? ldexpf(x[k], -my_e) : 0.0f;  // exact (see k_cos_prepare)
         const _Float16 h = (_Float16)v;
         hi[u] = h;
         lo[u] = (_Float16)(v - (float)h);

@@ -158,7 +158,7 @@ int hq_cosine_scores_dt(int dtype, const void* a, int Q, const void* b, int64_t 
   if (Q < 0 || N < 0 || K < 0) return fail(HQ_E_INVALID, "bad shape");
   if (dtype != HQ_F32 && dtype != HQ_F64) return fail(HQ_E_UNSUPPORTED, "dtype %d (float32 / float64)", dtype);
   if (Q == 0 || N == 0) return HQ_OK;
-  if (!a || !b || !out) return fail(HQ_E_INVALID, "null buffer");
+  if ((K > 0 && (!a || !b)) || !out) return fail(HQ_E_INVALID, "null buffer");  // K = 0: rows are never read
   const int g = grid_for((int64_t)Q * N, 256);
   if (dtype == HQ_F32)
     hipLaunchKernelGGL(k_cosine_t<float>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const float*)a, Q,
@@ -213,8 +213,9 @@ int hq_spatial_locality(int dtype, const void* q, int Q, const void* c, int64_t 
 int hq_threshold_select(const double* scores, const int64_t* ids, int Q, int64_t N, double threshold, int64_t cap,
                         int64_t* out_ids, int64_t* out_count, hq_stream_t stream) {
   if (Q < 0 || N < 0 || cap < 0) return fail(HQ_E_INVALID, "bad shape");
-  if (Q == 0 || cap == 0) return HQ_OK;
-  if ((N > 0 && !scores) || !out_ids || !out_count) return fail(HQ_E_INVALID, "null buffer");
+  if (Q == 0) return HQ_OK;
+  // cap = 0: every count is 0 and out_ids (no columns) is never touched
+  if ((N > 0 && cap > 0 && !scores) || (cap > 0 && !out_ids) || !out_count) return fail(HQ_E_INVALID, "null buffer");
   hipLaunchKernelGGL(k_threshold_select, dim3(Q < 8192 ? Q : 8192), dim3(64), 0, (hipStream_t)stream, scores, ids, Q,
                      N, threshold, cap, out_ids, out_count);
   HQ_CHECK_LAUNCH();

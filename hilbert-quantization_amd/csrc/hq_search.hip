@@ -6208,7 +6208,7 @@ int hq_pair_scores_raw_src(const double* q, const double* C, int64_t N, int m, i
 int hq_cosine_scores(const float* a, int Q, const float* b, int64_t N, int K, double* out, hq_stream_t stream) {
   if (Q < 0 || N < 0 || K < 0) return fail(HQ_E_INVALID, "bad shape");
   if (Q == 0 || N == 0) return HQ_OK;
-  if (!a || !b || !out) return fail(HQ_E_INVALID, "null buffer");
+  if ((K > 0 && (!a || !b)) || !out) return fail(HQ_E_INVALID, "null buffer");  // K = 0: rows are never read
   const int64_t total = (int64_t)Q * N;
   int64_t blocks = (total + 255) / 256;
   if (blocks > 16384) blocks = 16384;

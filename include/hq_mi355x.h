@@ -551,7 +551,17 @@ int hq_precomputed_similarity(const float* q_avgs, const float* q_norm, const fl
  *   inv [padded rows] = 1 / (scale |x|) (0 for a zero row).  Prepare a corpus once, each query batch per
  *   call, under the same cos_kernel option as the scoring call.
  * hq_cos_scores_mfma: out [Q, N] f64 = (cos + 1) / 2 (0 when a norm is 0), split-f16 MFMA contraction
- *   (v_mfma_f32_16x16x32_f16 x 3), within 1e-5 of the reference's float32 BLAS result.
+ *   (v_mfma_f32_16x16x32_f16 x 3), within 1e-5 of the exact cosine and of the reference's float32 BLAS result
+ *   for K <= 16384.  The error depends on the rows (profiles/cos_error_bounds.txt, measured per row family):
+ *   5e-8 where the products cancel (zero-mean rows, any K); same-sign rows (images, decoded u8 frames, post-ReLU
+ *   embeddings) grow with K, up to 1.4e-6 at K = 4096 and 3.2e-6 at K = 16384.
+ *   Input domain: every finite float32 row, subnormal rows (max |x| < 2^-126) and rows up to FLT_MAX included,
+ *   gives finite scores: the row is scaled by an exact power of two (ldexpf) and its norm is taken in float64.
+ *   Known, intended difference: a row so small that the reference's float32 norm underflows to 0 (all |x|
+ *   below about 3e-23) scores 0.0 there; here it is scored from its float64 norm like any other row, as
+ *   hq_cosine_scores does.  A row holding a NaN or an inf is outside the domain: its inverse norm is stored as
+ *   0, so all its scores are 0.0 and no other row's score changes (hq_cosine_scores / hq_cosine_scores_dt
+ *   return NaN for such a row, as the reference does).
  * hq_cos_scores_mfma_f32: the same scores rounded once to float32 (the reference's own score dtype; half
  *   the output bytes).                                                                           */
 int hq_cos_padded_k(int K);
@@ -591,7 +601,11 @@ int hq_cos_topk(const void* A16, const double* inv_a, int Q, const void* B16, co
  * hq_threshold_select: _apply_progressive_threshold (engine.py:243-287) for Q rows of candidate scores
  *   [Q, N] in the caller's order: the first `cap` candidates with score >= threshold -> out_ids [Q, cap]
  *   (ids[q, i] when ids is given, else the position i; -1 padded), out_count [Q].  The caller computes
- *   the level's threshold and cap exactly as the reference (Python float arithmetic).               */
+ *   the level's threshold and cap exactly as the reference (Python float arithmetic).  A NaN score never
+ *   passes.  cap = 0: every out_count[q] is written as 0 and out_ids, which then has no columns, is neither
+ *   read nor written (it may be NULL).
+ * hq_cosine_scores / hq_cosine_scores_dt with K = 0: every score is 0.0 (both norms are 0); a and b are not
+ *   read and may be NULL.                                                                            */
 int hq_cosine_scores_dt(int dtype, const void* a, int Q, const void* b, int64_t N, int K, double* out,
                         hq_stream_t stream);
 int hq_detect_heights(int dtype, const void* imgs, int64_t N, int H, int W, int* out, hq_stream_t stream);
