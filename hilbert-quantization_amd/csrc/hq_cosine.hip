@@ -30,6 +30,9 @@
 // passing frames of every (query, 384-frame tile) in its epilogue instead of storing scores; k_cos_topk_merge
 // reduces the tiles' sorted lists 64 at a time.  Same accumulators, same epilogue expression, same total order
 // as hq_select_topk on the dense matrix: identical ids, order and score bits, memory O(Q k N / 384).
+//
+// Compressed-domain search (hq_cosq_*; the last section of this file): the same tile, ping-pong,
+// top-k epilogue and merge on the store's own u8 frames + (min, max), contracted exactly by v_mfma_i32_16x16x64_i8.
 #include "hq_common.h"
 
 #include <stdlib.h>
@@ -1064,6 +1067,370 @@ int hq_cos_topk(const void* A16, const double* inv_a, int Q, const void* B16, co
   int64_t Pc = P;
   int cur = 0;
   for (;;) {
+    const int64_t P2 = (Pc + 63) / 64;
+    const bool last = P2 == 1;
+    const int nxt = cur == 1 ? 2 : 1;
+    const int64_t g = (int64_t)Q * P2 < 65536 ? (int64_t)Q * P2 : 65536;
+    hipLaunchKernelGGL(k_cos_topk_merge, dim3((unsigned)g), dim3(64), 0, s, Q, Pc, P2, k, last ? id_base : (int64_t)0,
+                       (const double*)bs[cur], (const int64_t*)bi[cur], last ? out_score : bs[nxt], last ? out_id : bi[nxt]);
+    HQ_CHECK_LAUNCH();
+    if (last) break;
+    Pc = P2;
+    cur = nxt;
+  }
+  return HQ_OK;
+}
+
+}  // extern "C"
+
+// ======== compressed-domain frame search: exact cosine of u8 frames (hq_cosq_*) ==========
+// A stored frame is K bytes u plus float32 (mn, mx), x_i = mn + (mx - mn) u_i / 255.  With w = u - 128,
+// S = sum w, T = sum w^2 (exact integers), s = (mx - mn) / 255, m = mn + s (128 + S / K) (the row mean),
+// V = K T - S^2 and n^2 = K m^2 + s^2 V / K, the cosine of two dequantised frames is
+//   cos = K a_q a_c + b_q b_c t / K,   a = m / n, b = s / n, t = K P - S_q S_c, P = sum w_q w_c
+// (include/hq_mi355x.h has the contract).  P is what v_mfma_i32_16x16x64_i8 accumulates, exactly, so the score
+// does not depend on tile shape, K order or kernel form.  hq_cosq_prepare stores, per row, the signed bytes in
+// 1 KiB operand fragments and the pre-scaled pair A = m / sqrt(n^2 / K), B = s / (K sqrt(n^2 / K)), so that
+// cos = A_q A_c + (B_q B_c) t: four float64 roundings per pair after exact integer work.
+// Operand map: fragment (16-row tile t, K step kb of 64) = 1024 bytes at (t KB + kb) 1024, lane 16 g + j holds
+// row 16 t + j, bytes 64 kb + 16 g .. + 15.  Queries and frames use the same fragment layout and the A and B
+// operands of the instruction pair up the same (lane group, byte) positions, so P sums over every k of the step
+// whatever order the hardware gives them inside it; only "lane & 15 = row" is relied on.
+namespace hq {
+
+typedef int i4v __attribute__((ext_vector_type(4)));
+
+constexpr int kCosqK = 64;        // K per step
+constexpr int kCosqMaxK = 65536;  // |P| <= 2^30, K T and S_q S_c below 2^48
+
+struct CosqArgs {
+  CosArgs c;         // Q, N, qtiles, ntiles, out, tk_*: what the shared epilogue pieces read (the rest unused)
+  const int8_t* A8;  // query fragments
+  const int8_t* B8;  // frame fragments
+  const double* sa;  // [Qp, 4]: A, B, S, ok (1.0 / 0.0)
+  const double* sb;  // [Np, 4]
+  int K;             // the true K (the formulas never see the padded one)
+  int KB;            // K steps
+};
+
+// The one pair expression of every epilogue (dense and fused agree bit for bit).  K P and S_q S_c are integers
+// below 2^48, so both products and their difference are exact in float64: t is the int64 value K P - S_q S_c.
+__device__ __forceinline__ double cosq_score(int P, double Kd, double Aq, double Bq, double Sq, double okq, double Ac,
+                                             double Bc, double Sc, double okc) {
+  const double t = Kd * (double)P - Sq * Sc;
+  const double cs = Aq * Ac + (Bq * Bc) * t;
+  return (okq != 0.0 && okc != 0.0) ? (cs + 1.0) / 2.0 : 0.0;
+}
+
+// One 16-wave workgroup per 16-row tile, one pass over the bytes: the waves split the tile's K steps, lane
+// 16 g + j flips (u ^ 0x80) row j's bytes 64 kb + 16 g .. + 15 and stores them at its place in the fragment
+// (one contiguous 1 KiB wave store), keeping int32 partial sums of w and w^2 (|S| <= 2^23, T <= 2^30); the
+// partials meet in LDS and sixteen threads write the rows' statistics (V in int64).  fast: base and ld are
+// multiples of 16, so a whole 16-byte piece inside K is one load; every other piece goes byte by byte.
+__global__ __launch_bounds__(1024) void k_cosq_prepare(const uint8_t* __restrict__ X, int64_t N, int64_t ld, int K,
+                                                       int KB, int64_t rows_out, const float* __restrict__ mm,
+                                                       int8_t* __restrict__ X8, double* __restrict__ st, int fast) {
+  __shared__ int sS[16], sT[16];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, j = lane & 15, g = lane >> 4;
+  for (int64_t t = blockIdx.x; t < rows_out / 16; t += gridDim.x) {
+    if (threadIdx.x < 16) sS[threadIdx.x] = sT[threadIdx.x] = 0;
+    __syncthreads();
+    const int64_t r = 16 * t + j;
+    const uint8_t* x = X + (r < N ? r : 0) * ld;
+    int S = 0, T = 0;
+    for (int kb = wv; kb < KB; kb += 16) {
+      const int k0 = kCosqK * kb + 16 * g;
+      uint32_t w[4] = {0u, 0u, 0u, 0u};  // pad rows and pad positions: w = 0
+      if (r < N && k0 < K) {
+        if (fast && k0 + 16 <= K) {
+          const uint4 v = *reinterpret_cast<const uint4*>(x + k0);
+          w[0] = v.x ^ 0x80808080u;
+          w[1] = v.y ^ 0x80808080u;
+          w[2] = v.z ^ 0x80808080u;
+          w[3] = v.w ^ 0x80808080u;
+        } else {
+#pragma unroll
+          for (int u = 0; u < 16; ++u)
+            if (k0 + u < K) w[u >> 2] |= (uint32_t)(x[k0 + u] ^ 0x80u) << (8 * (u & 3));
+        }
+      }
+#pragma unroll
+      for (int d = 0; d < 4; ++d)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+          const int v = (int)(int8_t)(w[d] >> (8 * b));
+          S += v;
+          T += v * v;
+        }
+      *reinterpret_cast<uint4*>(X8 + ((t * KB + kb) * 1024 + 16 * lane)) = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+    S += __shfl_xor(S, 16, 64);
+    T += __shfl_xor(T, 16, 64);
+    S += __shfl_xor(S, 32, 64);
+    T += __shfl_xor(T, 32, 64);
+    if (g == 0) {
+      atomicAdd(&sS[j], S);
+      atomicAdd(&sT[j], T);
+    }
+    __syncthreads();
+    if (threadIdx.x < 16) {
+      const int64_t row = 16 * t + threadIdx.x;
+      double A = 0.0, B = 0.0, ok = 0.0;
+      const int64_t Si = sS[threadIdx.x], Ti = sT[threadIdx.x];
+      if (row < N) {
+        const float fmn = mm[2 * row], fmx = mm[2 * row + 1];
+        if (isfinite(fmn) && isfinite(fmx)) {
+          const double mn = fmn, mx = fmx, Kd = K;
+          const double s = mx == mn ? 0.0 : (mx - mn) / 255.0;
+          const double m = mn + s * (128.0 + (double)Si / Kd);
+          const int64_t V = (int64_t)K * Ti - Si * Si;  // >= 0 (Cauchy-Schwarz), below 2^47
+          const double n2 = m * m + (s * s) * ((double)V / (Kd * Kd));  // n^2 / K
+          if (n2 > 0.0) {
+            const double inv = 1.0 / sqrt(n2);
+            A = m * inv;
+            B = (s * inv) / Kd;
+            ok = 1.0;
+          }
+        }
+      }
+      double* o = st + 4 * row;
+      o[0] = A;
+      o[1] = B;
+      o[2] = (double)Si;
+      o[3] = ok;
+    }
+    __syncthreads();  // sS / sT are cleared for the next tile
+  }
+}
+
+// The GEMM: k_cos_t<3, 1, 1>'s structure (128 queries x 384 frames per 8-wave workgroup, wave w = all 128
+// queries x frames 48 w .. + 47, frame fragments straight from global memory one K step ahead, query fragments
+// through two LDS stages, ping-pong: the two waves of a SIMD one barrier phase apart) with one operand plane,
+// K steps of 64 and v_mfma_i32_16x16x64_i8 into int32 accumulators.  Per K step and wave: 8 ds_read_b128,
+// 1 ds_write_b128, 1 + 3 global loads of 1 KiB, 24 MFMAs.  EP 0: float64 score stores; EP 4: the staged top-k
+// epilogue of hq_cos_topk (cos_topk_row on the same slab layout, running-threshold hint included).
+template <int EP>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_cosq_t(CosqArgs a, int64_t ftiles) {
+  constexpr int FT = 3, QT = 8, TN = 8 * 16 * FT;
+  // the epilogue's stage (8 wave slices of 16 x 48 f64); during the K loop its first 16 KiB hold the two query stages
+  __shared__ __attribute__((aligned(16))) uint8_t smem[8 * 16 * 16 * FT * 8];
+  int8_t(*sA)[QT * 1024] = reinterpret_cast<int8_t(*)[QT * 1024]>(smem);
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int64_t blk = blockIdx.x;
+  const int64_t xcd = blk & 7, slot = blk >> 3;
+  const int qt = (int)(slot % a.c.qtiles);
+  const int64_t nt = xcd + 8 * (slot / a.c.qtiles);
+  if (nt >= a.c.ntiles) return;
+  const int KB = a.KB;
+  const int64_t qt0 = (int64_t)qt * QT;
+  // wave w stages query tile w of every step
+  const int8_t* srcA = a.A8 + (qt0 + wv) * KB * 1024 + 16 * lane;
+  const int8_t* srcB[FT];
+#pragma unroll
+  for (int j = 0; j < FT; ++j) {
+    int64_t t = nt * (TN / 16) + wv * FT + j;
+    if (t > ftiles - 1) t = ftiles - 1;  // the last frame tile may pass the padded rows
+    srcB[j] = a.B8 + t * KB * 1024 + 16 * lane;
+  }
+  i4v ra;
+  i4v rb0[FT], rb1[FT];  // frame fragments of steps s, s + 1
+  auto loadA = [&](int kb) { ra = *reinterpret_cast<const i4v*>(srcA + (int64_t)kb * 1024); };
+  auto loadB = [&](int kb, i4v (&d)[FT]) {
+#pragma unroll
+    for (int j = 0; j < FT; ++j) d[j] = *reinterpret_cast<const i4v*>(srcB[j] + (int64_t)kb * 1024);
+  };
+  auto storeA = [&](int st) { *reinterpret_cast<i4v*>(&sA[st][wv * 1024 + 16 * lane]) = ra; };
+  i4v acc[QT][FT];
+#pragma unroll
+  for (int i = 0; i < QT; ++i)
+#pragma unroll
+    for (int j = 0; j < FT; ++j) acc[i][j] = i4v{0, 0, 0, 0};
+
+  // one K step: b = frame fragments of step s, nb receives step s + 1 (k_cos_t's step, PP = 1, D = 1; past the
+  // end the loads repeat the last step and the store fills a stage nobody reads again)
+  auto step = [&](int s, const i4v (&b)[FT], i4v (&nb)[FT]) {
+    const int st = s & 1;
+    storeA(st ^ 1);
+    loadA(s + 2 < KB ? s + 2 : KB - 1);
+    loadB(s + 1 < KB ? s + 1 : KB - 1, nb);
+    __builtin_amdgcn_sched_barrier(0);
+    i4v af[QT];
+#pragma unroll
+    for (int i = 0; i < QT; ++i) af[i] = *reinterpret_cast<const i4v*>(&sA[st][i * 1024 + 16 * lane]);
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < QT; ++i)
+#pragma unroll
+      for (int j = 0; j < FT; ++j)
+        acc[i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[i], b[j], acc[i][j], 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_barrier" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+  };
+
+  loadA(0);
+  loadB(0, rb0);
+  storeA(0);
+  loadA(KB > 1 ? 1 : 0);
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  // ping-pong as in k_cos_t: group 1 (waves 4-7) one barrier phase behind, group 0 one extra barrier at the end
+  const int grp = __builtin_amdgcn_readfirstlane(wv >> 2);
+  if (grp) asm volatile("s_barrier" ::: "memory");
+  int s = 0;
+  for (; s + 2 <= KB; s += 2) {
+    step(s, rb0, rb1);
+    step(s + 1, rb1, rb0);
+  }
+  if (s < KB) step(s, rb0, rb1);
+  if (!grp) asm volatile("s_barrier" ::: "memory");
+  // epilogue: lane holds queries 16 i + 4 (lane >> 4) + r, frames 16 j + (lane & 15) of its wave's columns (the
+  // C / D map does not depend on the operand type); sa / sb cover the padded rows, a frame column past them is
+  // clamped for the load and never stored
+  const int64_t q0 = qt0 * 16, n0 = nt * TN + (int64_t)wv * 16 * FT;
+  const int64_t nrows = ftiles * 16;
+  const double Kd = (double)a.K;
+  double4 sc[FT];
+#pragma unroll
+  for (int j = 0; j < FT; ++j) {
+    const int64_t n = n0 + 16 * j + (lane & 15);
+    sc[j] = *reinterpret_cast<const double4*>(a.sb + 4 * (n < nrows ? n : nrows - 1));
+  }
+  double* stage = reinterpret_cast<double*>(smem) + wv * 16 * 16 * FT;
+#pragma unroll
+  for (int i = 0; i < QT; ++i) {
+    const int64_t qb = q0 + 16 * i + 4 * (lane >> 4);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int64_t q = qb + r;
+      const double4 sq = *reinterpret_cast<const double4*>(a.sa + 4 * q);
+#pragma unroll
+      for (int j = 0; j < FT; ++j) {
+        const int64_t n = n0 + 16 * j + (lane & 15);
+        const double v = cosq_score(acc[i][j][r], Kd, sq.x, sq.y, sq.z, sq.w, sc[j].x, sc[j].y, sc[j].z, sc[j].w);
+        if constexpr (EP == 4) {  // top-k: every value is staged, rows and columns are masked in cos_topk_row
+          stage[(4 * (lane >> 4) + r) * 16 * FT + 16 * j + (lane & 15)] = v;
+        } else if (q < a.c.Q && n < a.c.N) {
+          __builtin_nontemporal_store(v, a.c.out + q * a.c.N + n);  // write-once scores
+        }
+      }
+    }
+    if constexpr (EP == 4) {
+      // as k_cos_t's EP 4: wave w selects for queries 2 w and 2 w + 1 of the row block; every wave of the
+      // workgroup reaches both barriers of every row block
+      __syncthreads();
+#pragma unroll 1
+      for (int h = 0; h < 2; ++h) {
+        const int row = 2 * wv + h;
+        const int64_t q = q0 + 16 * i + row;
+        if (q < a.c.Q) cos_topk_row<TN>(reinterpret_cast<const double*>(smem), row, q, nt, a.c);
+      }
+      __syncthreads();  // the next row block overwrites the stage
+    }
+  }
+}
+
+template <int EP>
+static int launch_cosq(CosqArgs a, hipStream_t s) {
+  const int64_t np_rows = hq_cosq_padded_rows(a.c.N);
+  a.c.qtiles = (int)(hq_cosq_padded_rows(a.c.Q) / 128);
+  a.c.ntiles = (np_rows + 383) / 384;
+  const int64_t nt8 = ((a.c.ntiles + 7) / 8) * 8;
+  const int64_t blocks = nt8 * a.c.qtiles;
+  if (blocks > 0x7FFFFFFF) return fail(HQ_E_UNSUPPORTED, "too many tiles");
+  hipLaunchKernelGGL(k_cosq_t<EP>, dim3((unsigned)blocks), dim3(512), 0, s, a, np_rows / 16);
+  HQ_CHECK_LAUNCH();
+  return HQ_OK;
+}
+
+static CosqArgs cosq_args(const void* A8, const double* sa, int Q, const void* B8, const double* sb, int64_t N, int K) {
+  CosqArgs a;
+  memset(&a, 0, sizeof(a));
+  a.A8 = reinterpret_cast<const int8_t*>(A8);
+  a.B8 = reinterpret_cast<const int8_t*>(B8);
+  a.sa = sa;
+  a.sb = sb;
+  a.K = K;
+  a.KB = hq_cosq_padded_k(K) / kCosqK;
+  a.c.Q = Q;
+  a.c.N = N;
+  return a;
+}
+
+}  // namespace hq
+
+extern "C" {
+
+int hq_cosq_padded_k(int K) { return K <= 0 ? 0 : ((K + kCosqK - 1) / kCosqK) * kCosqK; }
+int64_t hq_cosq_padded_rows(int64_t N) { return N <= 0 ? 0 : ((N + kCosT - 1) / kCosT) * kCosT; }
+
+int hq_cosq_prepare(const uint8_t* frames, int64_t N, int64_t ld, int K, const float* minmax, void* X8, double* stats,
+                    hq_stream_t stream) {
+  if (N < 0 || K <= 0 || ld < K) return fail(HQ_E_INVALID, "bad shape N=%lld K=%d ld=%lld", (long long)N, K, (long long)ld);
+  if (N == 0) return HQ_OK;
+  if (K > kCosqMaxK) return fail(HQ_E_UNSUPPORTED, "K=%d: the int32 accumulator holds K <= %d", K, kCosqMaxK);
+  if (!frames || !minmax || !X8 || !stats) return fail(HQ_E_INVALID, "null buffer");
+  const int64_t rows = hq_cosq_padded_rows(N);
+  int64_t blocks = rows / 16;
+  if (blocks > 65536) blocks = 65536;
+  const int fast = ((uintptr_t)frames % 16 == 0 && ld % 16 == 0) ? 1 : 0;
+  hipLaunchKernelGGL(k_cosq_prepare, dim3((unsigned)blocks), dim3(1024), 0, (hipStream_t)stream, frames, N, ld, K,
+                     hq_cosq_padded_k(K) / kCosqK, rows, minmax, reinterpret_cast<int8_t*>(X8), stats, fast);
+  HQ_CHECK_LAUNCH();
+  return HQ_OK;
+}
+
+int hq_cosq_scores(const void* A8, const double* stats_a, int Q, const void* B8, const double* stats_b, int64_t N, int K,
+                   double* out, hq_stream_t stream) {
+  if (Q < 0 || N < 0 || K <= 0) return fail(HQ_E_INVALID, "bad shape Q=%d N=%lld K=%d", Q, (long long)N, K);
+  if (Q == 0 || N == 0) return HQ_OK;
+  if (K > kCosqMaxK) return fail(HQ_E_UNSUPPORTED, "K=%d: the int32 accumulator holds K <= %d", K, kCosqMaxK);
+  if (!A8 || !stats_a || !B8 || !stats_b || !out) return fail(HQ_E_INVALID, "null buffer");
+  CosqArgs a = cosq_args(A8, stats_a, Q, B8, stats_b, N, K);
+  a.c.out = out;
+  return launch_cosq<0>(a, (hipStream_t)stream);
+}
+
+// The workspace layout and the merge stage are hq_cos_topk's: [Q] hint keys, the stage-1 slab [Q, P, k] and
+// two merge buffers (P = frame tiles of 384).
+size_t hq_cosq_topk_workspace_size(int Q, int64_t N, int k) { return hq_cos_topk_workspace_size(Q, N, k); }
+
+int hq_cosq_topk(const void* A8, const double* stats_a, int Q, const void* B8, const double* stats_b, int64_t N, int K,
+                 int k, double threshold, int thr_mode, int64_t id_base, void* workspace, size_t workspace_bytes,
+                 double* out_score, int64_t* out_id, hq_stream_t stream) {
+  if (Q < 0 || N < 0 || K <= 0 || k < 1) return fail(HQ_E_INVALID, "bad shape Q=%d N=%lld K=%d k=%d", Q, (long long)N, K, k);
+  if (Q == 0 || N == 0) return HQ_OK;
+  if (k > 64) return fail(HQ_E_UNSUPPORTED, "k=%d: the fused frame top-k keeps lists of at most 64", k);
+  if (K > kCosqMaxK) return fail(HQ_E_UNSUPPORTED, "K=%d: the int32 accumulator holds K <= %d", K, kCosqMaxK);
+  if (!A8 || !stats_a || !B8 || !stats_b || !workspace || !out_score || !out_id) return fail(HQ_E_INVALID, "null buffer");
+  if (workspace_bytes < hq_cosq_topk_workspace_size(Q, N, k)) return fail(HQ_E_INVALID, "workspace too small");
+  const hipStream_t s = (hipStream_t)stream;
+  const int64_t P = cos_topk_tiles(N);
+  uint8_t* w = reinterpret_cast<uint8_t*>(workspace);
+  auto take = [&](size_t bytes) { uint8_t* p = w; w += cos_topk_al(bytes); return p; };
+  uint64_t* hint = reinterpret_cast<uint64_t*>(take((size_t)Q * 8));
+  double* bs[3];
+  int64_t* bi[3];
+  int64_t cap = P;  // lists per query a buffer holds: P, ceil(P / 64), ceil(P / 4096)
+  for (int i = 0; i < 3; ++i) {
+    bs[i] = reinterpret_cast<double*>(take((size_t)Q * cap * k * 8));
+    bi[i] = reinterpret_cast<int64_t*>(take((size_t)Q * cap * k * 8));
+    cap = (cap + 63) / 64;
+  }
+  CosqArgs a = cosq_args(A8, stats_a, Q, B8, stats_b, N, K);
+  a.c.tk_s = bs[0];
+  a.c.tk_id = bi[0];
+  a.c.tk_hint = opt(OPT_COS_TOPK_HINT, 1) ? hint : nullptr;
+  a.c.tk_thr = threshold;
+  a.c.tk_mode = thr_mode;
+  a.c.tk_k = k;
+  if (a.c.tk_hint) HQ_CHECK_HIP(hipMemsetAsync(hint, 0, (size_t)Q * 8, s));
+  const int rc = launch_cosq<4>(a, s);
+  if (rc != HQ_OK) return rc;
+  int64_t Pc = P;
+  int cur = 0;
+  for (;;) {  // merge 64 lists at a time until one is left, as hq_cos_topk does
     const int64_t P2 = (Pc + 63) / 64;
     const bool last = P2 == 1;
     const int nxt = cur == 1 ? 2 : 1;

@@ -1084,3 +1084,112 @@ def cosine_scores(a, b, exc=None):
     if Q * N * max(K, 1) >= MFMA_COS_MIN_WORK and K > 0:
         return cosine_scores_mfma(cos_prepare(a2[:, :K], exc), cos_prepare(b2[:, :K], exc), exc)
     return cosine_scores_f64(a, b, exc)
+
+
+# ------------------------------------------------ compressed-domain frame search (u8 frames, exact)
+
+
+class CosQRows:
+    """u8 rows prepared for the exact integer cosine (hq_cosq_prepare): X8 [Np, Kp] signed bytes in 1 KiB i8 MFMA
+    operand fragments, stats [Np, 4] f64 (pre-scaled a, b, S, inv != 0): one byte per value resident where the
+    split-f16 rows of the decoded frames hold four."""
+
+    __slots__ = ("X8", "stats", "N", "K")
+
+    def __init__(self, X8, stats, N, K):
+        self.X8, self.stats, self.N, self.K = X8, stats, int(N), int(K)
+
+    @property
+    def nbytes(self) -> int:
+        return self.X8.numel() * self.X8.element_size() + self.stats.numel() * self.stats.element_size()
+
+
+def cosq_prepare(frames, minmax, rows: Optional[int] = None, exc=None) -> CosQRows:
+    """u8 frames [N, r, c] (or rows [N, K]) with minmax f32 [N, 2] -> CosQRows of the first `rows` rows of every
+    frame (all of them by default).  The frames are read in place: K = rows * c bytes out of every r * c."""
+    t = torch()
+    if frames.dtype != t.uint8:
+        raise TypeError("cosq_prepare expects uint8 frames (quantise float32 rows with map_index_quantize / quantize_u8)")
+    if frames.dim() < 2:
+        raise ValueError("frames must be [N, ...]")
+    N = int(frames.shape[0])
+    if frames.dim() == 2:
+        if rows is not None:
+            raise ValueError("rows= needs frames [N, r, c]")
+        x2 = frames if frames.stride(-1) == 1 else frames.contiguous()
+        K = int(x2.shape[1])
+    else:
+        r, c = int(frames.shape[1]), int(np.prod(frames.shape[2:]))
+        rows = r if rows is None else int(rows)
+        if not 1 <= rows <= r:
+            raise ValueError(f"rows = {rows} of {r}")
+        x2 = _contig(frames).view(N, r * c)
+        K = rows * c
+    mm = _contig(minmax.reshape(-1, 2).to(t.float32))
+    if int(mm.shape[0]) != N:
+        raise ValueError(f"{int(mm.shape[0])} (min, max) pairs for {N} frames")
+    Kp = int(_L().hq_cosq_padded_k(K))
+    Np = int(_L().hq_cosq_padded_rows(N))
+    X8 = t.empty((max(Np, 1), max(Kp, 1)), dtype=t.int8, device=x2.device)
+    stats = t.empty((max(Np, 1), 4), dtype=t.float64, device=x2.device)
+    if N:
+        _chk(_L().hq_cosq_prepare(ptr(x2), N, x2.stride(0) if N > 1 else int(x2.shape[1]), K, ptr(mm), ptr(X8),
+                                  ptr(stats), stream()), exc)
+    return CosQRows(X8, stats, N, K)
+
+
+def cosq_scores(q: CosQRows, c: CosQRows, exc=None):
+    """(cos + 1) / 2 of the dequantised rows, every prepared query against every prepared frame -> f64 [Q, N],
+    within a few float64 roundings of the exact value (hq_cosq_scores: an exact int8 MFMA contraction)."""
+    t = torch()
+    if q.K != c.K:
+        raise ValueError(f"query length {q.K} != frame length {c.K}")
+    out = t.empty((q.N, c.N), dtype=t.float64, device=q.X8.device)
+    _chk(_L().hq_cosq_scores(ptr(q.X8), ptr(q.stats), q.N, ptr(c.X8), ptr(c.stats), c.N, q.K, ptr(out), stream()), exc)
+    return out
+
+
+def _cosq_query_block(q: CosQRows, q0: int, q1: int) -> CosQRows:
+    """Prepared queries [q0, q1), q0 a multiple of 16 (fragments are tile-major: a block is a pointer offset)."""
+    return q if (q0 == 0 and q1 == q.N) else CosQRows(q.X8[q0:], q.stats[q0:], q1 - q0, q.K)
+
+
+def cosq_topk(q: CosQRows, c: CosQRows, k: int, threshold: float = 0.0, thr_mode: int = 0, id_base: int = 0,
+              workspace_limit: int = 256 << 20, exc=None):
+    """The k nearest prepared u8 frames of every prepared u8 query -> (scores [Q, k] f64, ids [Q, k] i64), equal to
+    select_topk(cosq_scores(q, c), k, threshold, thr_mode, id_base) in ids, order and score bits (hq_cosq_topk).
+    Workspace, query blocks under workspace_limit and the dense route for k > 64 or k > N: as cosine_topk."""
+    t = torch()
+    if q.K != c.K:
+        raise ValueError(f"query length {q.K} != frame length {c.K}")
+    k, Q, N = int(k), q.N, c.N
+    if k < 1:
+        raise ValueError(f"k = {k}")
+    dev = q.X8.device
+    os_ = t.full((Q, k), float("-inf"), dtype=t.float64, device=dev)
+    oi = t.full((Q, k), -1, dtype=t.int64, device=dev)
+    if Q == 0 or N == 0:
+        return os_, oi
+    limit = max(int(workspace_limit), 1)
+    if k > 64 or k > N:
+        per = max(128, limit // (8 * N) // 128 * 128)
+        for q0 in range(0, Q, per):
+            q1 = min(Q, q0 + per)
+            s, i, _, _ = select_topk(cosq_scores(_cosq_query_block(q, q0, q1), c, exc), k, threshold, thr_mode,
+                                     id_base, exc)
+            os_[q0:q1], oi[q0:q1] = s, i
+        return os_, oi
+    size = _L().hq_cosq_topk_workspace_size
+    per = Q
+    if int(size(Q, N, k)) > limit:
+        per = max(128, limit // max(int(size(128, N, k)), 1) * 128)
+        while per > 128 and int(size(per, N, k)) > limit:
+            per -= 128
+    for q0 in range(0, Q, per):
+        q1 = min(Q, q0 + per)
+        b = _cosq_query_block(q, q0, q1)
+        wb = int(size(b.N, N, k))
+        ws = _workspace(wb, dev)
+        _chk(_L().hq_cosq_topk(ptr(b.X8), ptr(b.stats), b.N, ptr(c.X8), ptr(c.stats), N, q.K, k, float(threshold),
+                               int(thr_mode), int(id_base), ptr(ws), wb, ptr(os_[q0:q1]), ptr(oi[q0:q1]), stream()), exc)
+    return os_, oi

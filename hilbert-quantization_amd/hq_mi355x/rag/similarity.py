@@ -85,6 +85,72 @@ class FrameCosineCorpus:
         return K.cosine_topk(K.cos_prepare(q2), self._rows, int(k), thr, mode)
 
 
+class QuantizedFrameCorpus:
+    """The store's own u8 frames [N, r, c] with their (min, max) pairs [N, 2], prepared once for the exact
+    integer cosine (hq_cosq_prepare) and searched without decoding: only the signed bytes (1 B per value, in
+    int8 MFMA operand fragments) and four float64 statistics per frame stay resident.
+
+    The score of a (query, frame) pair is (cos + 1) / 2 of the two dequantised frames, x = mn + (mx - mn) u / 255,
+    within a few float64 roundings of the exact value (the contraction is an exact int32 sum); a frame whose
+    (mn, mx) is not finite scores 0.0.  `rows` is how many leading rows of every frame are compared: by default
+    c when r == c + 1 (the pipeline's frames, index row left out), else r.  rows * c <= 65536.
+
+    Queries must be u8 frames with their own (min, max) too: search() takes them as they are,
+    search_parameters() quantises float32 parameters with map_index_quantize at the corpus's n first.  Float32
+    query frames against a u8 corpus without quantising them are out of scope (FrameCosineCorpus does that on
+    decoded frames)."""
+
+    def __init__(self, frames_u8, minmax, rows=None):
+        t = torch()
+        x = to_dev(frames_u8)
+        if x.dim() != 3 or x.dtype != t.uint8:
+            raise ValueError("frames_u8 must be uint8 [N, r, c]")
+        r, c = int(x.shape[1]), int(x.shape[2])
+        if rows is None:
+            rows = c if r == c + 1 else r
+        self.rows = int(rows)
+        self.shape = (r, c)
+        self._rows = K.cosq_prepare(x, to_dev(minmax), self.rows)
+
+    @classmethod
+    def from_parameters(cls, x, n: int):
+        """Float32 parameters [N, d] -> the pipeline's (n + 1) x n u8 frames (map_index_quantize) -> corpus."""
+        frames, _, mm = K.map_index_quantize(to_dev(x), int(n), want_idx=False)
+        return cls(frames, mm)
+
+    @property
+    def N(self) -> int:
+        return self._rows.N
+
+    @property
+    def K(self) -> int:
+        return self._rows.K
+
+    def __len__(self) -> int:
+        return self._rows.N
+
+    @property
+    def resident_bytes(self) -> int:
+        return self._rows.nbytes
+
+    def search(self, query_frames_u8, query_minmax, k: int = 10, threshold=None):
+        """u8 query frames [Q, r, c] (or one [r, c]; r >= the corpus's rows, same c) with minmax [Q, 2] -> device
+        (scores [Q, k] f64, ids [Q, k] i64), (score desc, frame asc), -inf / -1 where fewer than k frames pass
+        `threshold` (None: no test; else score >= threshold)."""
+        q = to_dev(query_frames_u8)
+        if q.dim() == 2:
+            q = q.unsqueeze(0)
+        if q.dim() != 3 or int(q.shape[2]) != self.shape[1] or int(q.shape[1]) < self.rows:
+            raise ValueError(f"query frames {tuple(q.shape)} do not hold {self.rows} rows of {self.shape[1]}")
+        thr, mode = _threshold_mode(threshold)
+        return K.cosq_topk(K.cosq_prepare(q, to_dev(query_minmax), self.rows), self._rows, int(k), thr, mode)
+
+    def search_parameters(self, x, k: int = 10, threshold=None):
+        """Float32 parameters [Q, d]: quantised like the store (map_index_quantize at n = c), then search()."""
+        frames, _, mm = K.map_index_quantize(to_dev(x), self.shape[1], want_idx=False)
+        return self.search(frames, mm, k, threshold)
+
+
 def calculate_embedding_cosine_similarity(embedding1, embedding2) -> float:
     """engine.py:622-660: flatten, truncate to the common length, (cos + 1) / 2, 0 for a zero norm."""
     e1, e2 = np.asarray(embedding1), np.asarray(embedding2)

@@ -588,6 +588,48 @@ int hq_cos_topk(const void* A16, const double* inv_a, int Q, const void* B16, co
                 void* workspace, size_t workspace_bytes,
                 double* out_score, int64_t* out_id, hq_stream_t stream);
 
+/* ---- compressed-domain frame search: exact cosine top-k on u8 frames ------------------------------
+ * The store's own format (hq_map_index_quantize / hq_quantize_u8: K bytes u and float32 (mn, mx) per frame,
+ * x_i = mn + (mx - mn) u_i / 255) is searched without decoding: the cosine of two dequantised frames is a
+ * closed form of exact integers and the two (mn, mx) pairs.  Queries must be u8 rows too (quantise them with
+ * hq_map_index_quantize / hq_quantize_u8); float32 queries against a u8 corpus are not offered.
+ * The contract, everything in float64 from the float32 (mn, mx):
+ *   row:  w_i = u_i - 128;  S = sum w_i, T = sum w_i^2 (exact integers);  s = (mx - mn) / 255 (0 when mx == mn);
+ *         m = mn + s (128 + S / K) (the row mean);  V = K T - S^2 (exact in int64, >= 0);  n^2 = K m^2 + s^2 V / K;
+ *         inv = 1 / sqrt(n^2), 0 when n^2 == 0 and 0 when mn or mx is not finite;  a = m inv, b = s inv.
+ *   pair: P = sum w_q,i w_c,i (the int32 accumulator of v_mfma_i32_16x16x64_i8);  t = K P - S_q S_c (exact);
+ *         cos = K a_q a_c + b_q b_c t / K;  score = (cos + 1) / 2, and 0.0 when either inv is 0.
+ *   A row with a non-finite mn or mx is outside the input domain: it scores 0.0 against everything and changes
+ *   no other score.  Every finite float32 (mn, mx), subnormal and near-FLT_MAX ranges included, is in the domain.
+ *   The integer part is exact, so the score does not depend on tile shape, K order or kernel form: it is within
+ *   a few float64 roundings (1e-13 is tested) of the cosine of the dequantised frames in extended precision.
+ *   Limits: 1 <= K <= 65536 (|P| <= 2^30; K T and S_q S_c below 2^48); a larger K: HQ_E_UNSUPPORTED.  Padded K
+ *   positions and padded rows hold w = 0 and the formulas use the true K.
+ * hq_cosq_prepare: frames u8 [N, K] (ld bytes between frames, ld >= K: a store of (n + 1) x n frames searched on
+ *   its n leading rows has ld = (n + 1) n, K = n n), minmax f32 [N, 2] -> X8: hq_cosq_padded_rows(N) x
+ *   hq_cosq_padded_k(K) signed bytes u ^ 0x80 in 1 KiB MFMA operand fragments (16-row tile t, K step kb of 64 at
+ *   (t KB + kb) 1024; lane 16 g + j = row 16 t + j, bytes 64 kb + 16 g .. + 15), and stats f64 [padded rows, 4] =
+ *   (m / sqrt(n^2 / K), s / (K sqrt(n^2 / K)), S, inv != 0), the pre-scaled a and b with which
+ *   cos = A_q A_c + (B_q B_c) t.  One launch, no host round trip.  16-byte loads when the base and ld are
+ *   multiples of 16, byte loads otherwise.
+ * hq_cosq_scores: out [Q, N] f64, the dense scores.
+ * hq_cosq_topk: arguments and semantics of hq_cos_topk on these operands (threshold, thr_mode 0 / 1 / 2, id_base,
+ *   -inf / -1 padding, 1 <= k <= 64 else HQ_E_UNSUPPORTED, (score descending, id ascending)); the lists equal
+ *   hq_select_topk_ws of hq_cosq_scores bit for bit, so duplicated frames tie exactly and list by id.
+ *   workspace: hq_cosq_topk_workspace_size(Q, N, k) bytes.
+ * Zero Q or N: HQ_OK before any pointer is looked at; negative sizes, K < 1, ld < K, NULL operands: HQ_E_INVALID. */
+int hq_cosq_padded_k(int K);
+int64_t hq_cosq_padded_rows(int64_t N);
+int hq_cosq_prepare(const uint8_t* frames, int64_t N, int64_t ld, int K, const float* minmax, void* X8, double* stats,
+                    hq_stream_t stream);
+int hq_cosq_scores(const void* A8, const double* stats_a, int Q, const void* B8, const double* stats_b, int64_t N,
+                   int K, double* out, hq_stream_t stream);
+size_t hq_cosq_topk_workspace_size(int Q, int64_t N, int k);
+int hq_cosq_topk(const void* A8, const double* stats_a, int Q, const void* B8, const double* stats_b, int64_t N,
+                 int K, int k, double threshold, int thr_mode, int64_t id_base,
+                 void* workspace, size_t workspace_bytes,
+                 double* out_score, int64_t* out_id, hq_stream_t stream);
+
 /* ---- S7: the rest of the RAG scorer (rag/search/engine.py) --------------------------------------
  * hq_cosine_scores_dt: as hq_cosine_scores for float32 (HQ_F32) or float64 (HQ_F64) rows; float64
  *   inputs are not narrowed (engine.py:622-660 computes in the input dtype).
