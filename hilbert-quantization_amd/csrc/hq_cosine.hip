@@ -31,8 +31,10 @@
 // reduces the tiles' sorted lists 64 at a time.  Same accumulators, same epilogue expression, same total order
 // as hq_select_topk on the dense matrix: identical ids, order and score bits, memory O(Q k N / 384).
 //
-// Compressed-domain search (hq_cosq_*; the last section of this file): the same tile, ping-pong,
+// Compressed-domain search (hq_cosq_*; the section before the last of this file): the same tile, ping-pong,
 // top-k epilogue and merge on the store's own u8 frames + (min, max), contracted exactly by v_mfma_i32_16x16x64_i8.
+// Float32 queries against that u8 corpus (hq_cosqf_*; the last section): the query as three int8
+// digit planes of a 24-bit fixed-point row, three exact int32 sums per pair, the same epilogue pieces.
 #include "hq_common.h"
 
 #include <stdlib.h>
@@ -1427,6 +1429,400 @@ int hq_cosq_topk(const void* A8, const double* stats_a, int Q, const void* B8, c
   a.c.tk_k = k;
   if (a.c.tk_hint) HQ_CHECK_HIP(hipMemsetAsync(hint, 0, (size_t)Q * 8, s));
   const int rc = launch_cosq<4>(a, s);
+  if (rc != HQ_OK) return rc;
+  int64_t Pc = P;
+  int cur = 0;
+  for (;;) {  // merge 64 lists at a time until one is left, as hq_cos_topk does
+    const int64_t P2 = (Pc + 63) / 64;
+    const bool last = P2 == 1;
+    const int nxt = cur == 1 ? 2 : 1;
+    const int64_t g = (int64_t)Q * P2 < 65536 ? (int64_t)Q * P2 : 65536;
+    hipLaunchKernelGGL(k_cos_topk_merge, dim3((unsigned)g), dim3(64), 0, s, Q, Pc, P2, k, last ? id_base : (int64_t)0,
+                       (const double*)bs[cur], (const int64_t*)bi[cur], last ? out_score : bs[nxt], last ? out_id : bi[nxt]);
+    HQ_CHECK_LAUNCH();
+    if (last) break;
+    Pc = P2;
+    cur = nxt;
+  }
+  return HQ_OK;
+}
+
+}  // extern "C"
+
+// ======== float32 queries against the u8 frame store: exact asymmetric cosine (hq_cosqf_*) ======
+// The corpus operands are hq_cosq_prepare's, untouched.  A query row of K float32 values is scaled by a power of
+// two and rounded to 24-bit fixed point: amax = f 2^e (f in [0.5, 1)), v_i = min(rint(q_i 2^(23 - e)), 2^23 - 1),
+// an integer vector that plays "a row with s = 1" in the closed form of hq_cosq_*: with Sv = sum v, Nv = sum v^2,
+// B_q = 1 / sqrt(K Nv), A_q = Sv B_q and D = sum v_i w_i,
+//   cos = A_q A_c + (B_q B_c) t,   t = K D - Sv S_c   (an exact int64, |t| <= 2^62).
+// D comes from three int8 digit planes of v contracted with the corpus's signed bytes by v_mfma_i32_16x16x64_i8:
+// with the two's-complement bytes of v (b2 signed, b1 and b0 unsigned), plane 2 = b2, plane 1 = b1 ^ 0x80 =
+// b1 - 128, plane 0 = b0 ^ 0x80 = b0 - 128, so v = 65536 p2 + 256 p1 + p0 + 32896 and
+//   D = 65536 P2 + 256 P1 + P0 + 32896 S_c,   |P_j| <= 2^30 for K <= 65536.
+// Pad rows and pad K positions hold 0 in all three planes (the corpus's pad bytes are w = 0 as well, and S_c is
+// the true-K sum, so the identity holds on the padded operands).
+// Operand map: query tile t (16 rows), K step kb, plane p = the 1 KiB fragment at ((t KB + kb) 3 + p) 1024 in the
+// corpus's fragment layout (lane 16 g + j = row 16 t + j, bytes 64 kb + 16 g .. + 15): a step's query operands are
+// one contiguous 3 KiB.  stats [padded rows, 4] = (A_q, B_q, Sv, ok); Sv is an integer below 2^39, exact as f64.
+namespace hq {
+
+constexpr int kCosqfQ = 64;  // queries per workgroup of k_cosqf_t = the row padding of the query operands
+
+// The one pair expression of every hq_cosqf_* epilogue.  The integer part wraps nowhere that matters: K D and
+// Sv S_c reach 2^62 each, their difference is at most 2^62 in magnitude (Cauchy-Schwarz on the two centred rows),
+// and unsigned arithmetic gives that difference whatever the intermediate carries do.
+__device__ __forceinline__ double cosqf_score(int P0, int P1, int P2, int64_t K, double Aq, double Bq, int64_t Sv,
+                                              double okq, double Ac, double Bc, int64_t Sc, double okc) {
+  const int64_t D = 65536 * (int64_t)P2 + 256 * (int64_t)P1 + (int64_t)P0 + 32896 * Sc;
+  const int64_t t = (int64_t)((uint64_t)K * (uint64_t)D - (uint64_t)Sv * (uint64_t)Sc);
+  const double cs = Aq * Ac + (Bq * Bc) * (double)t;
+  return (okq != 0.0 && okc != 0.0) ? (cs + 1.0) / 2.0 : 0.0;
+}
+
+// One 16-wave workgroup per 16-row query tile, two passes over the floats (the second one hits the cache).
+// Pass 1: the largest |q| bit pattern of every row (a NaN or inf is above every finite pattern, so one integer
+// max finds amax and the non-finite rows).  Pass 2: lane 16 g + j rounds row j's values 64 kb + 16 g .. + 15 to v
+// (the scaling in float64 is exact: 2^(23 - e) overflows float32 for subnormal rows), stores the three digit
+// pieces at its place in the step's three fragments and keeps int64 partial sums of v and v^2; the partials meet
+// in LDS and sixteen threads write the rows' statistics.  fast: base and ld are multiples of 16 bytes, so a whole
+// 16-value piece inside K is four 16-byte loads; every other piece goes element by element.
+__global__ __launch_bounds__(1024) void k_cosqf_prepare(const float* __restrict__ X, int64_t Q, int64_t ld, int K,
+                                                        int KB, int64_t rows_out, int8_t* __restrict__ Q8,
+                                                        double* __restrict__ st, int fast) {
+  __shared__ unsigned sM[16];
+  __shared__ unsigned long long sS[16], sN[16];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, j = lane & 15, g = lane >> 4;
+  for (int64_t t = blockIdx.x; t < rows_out / 16; t += gridDim.x) {
+    if (threadIdx.x < 16) {
+      sM[threadIdx.x] = 0u;
+      sS[threadIdx.x] = sN[threadIdx.x] = 0ull;
+    }
+    __syncthreads();
+    const int64_t r = 16 * t + j;
+    const float* x = X + (r < Q ? r : 0) * ld;
+    auto piece = [&](int k0, float (&f)[16]) {  // values k0 .. k0 + 15 of the row, 0 past K
+      if (fast && k0 + 16 <= K) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const float4 v = *reinterpret_cast<const float4*>(x + k0 + 4 * u);
+          f[4 * u] = v.x;
+          f[4 * u + 1] = v.y;
+          f[4 * u + 2] = v.z;
+          f[4 * u + 3] = v.w;
+        }
+      } else {
+#pragma unroll
+        for (int u = 0; u < 16; ++u) f[u] = k0 + u < K ? x[k0 + u] : 0.0f;
+      }
+    };
+    unsigned m = 0u;
+    if (r < Q)
+      for (int kb = wv; kb < KB; kb += 16) {
+        const int k0 = kCosqK * kb + 16 * g;
+        if (k0 < K) {
+          float f[16];
+          piece(k0, f);
+#pragma unroll
+          for (int u = 0; u < 16; ++u) {
+            const unsigned b = __float_as_uint(f[u]) & 0x7FFFFFFFu;
+            m = b > m ? b : m;
+          }
+        }
+      }
+    {
+      const unsigned m2 = (unsigned)__shfl_xor((int)m, 16, 64);
+      m = m2 > m ? m2 : m;
+      const unsigned m3 = (unsigned)__shfl_xor((int)m, 32, 64);
+      m = m3 > m ? m3 : m;
+    }
+    if (g == 0) atomicMax(&sM[j], m);
+    __syncthreads();
+    const unsigned am = sM[j];
+    const bool ok = r < Q && am != 0u && am < 0x7F800000u;
+    // amax = f 2^e, f in [0.5, 1): amax is a normal float64 whatever it was in float32
+    const int e = (int)((__double_as_longlong((double)__uint_as_float(am)) >> 52) & 0x7FF) - 1022;
+    const double scale = __longlong_as_double((long long)(1023 + 23 - e) << 52);  // 2^(23 - e), 23 - e in [-105, 172]
+    int64_t S = 0, Nn = 0;
+    for (int kb = wv; kb < KB; kb += 16) {
+      const int k0 = kCosqK * kb + 16 * g;
+      uint32_t d[3][4] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};  // pad rows, pad positions: 0
+      if (ok && k0 < K) {
+        float f[16];
+        piece(k0, f);
+#pragma unroll
+        for (int u = 0; u < 16; ++u)
+          if (k0 + u < K) {
+            int v = (int)rint((double)f[u] * scale);  // round to nearest even, |.| <= 2^23
+            v = v > 8388607 ? 8388607 : v;
+            S += v;
+            Nn += (int64_t)v * v;
+            const uint32_t b = (uint32_t)v ^ 0x8080u;
+            d[0][u >> 2] |= (b & 0xFFu) << (8 * (u & 3));
+            d[1][u >> 2] |= ((b >> 8) & 0xFFu) << (8 * (u & 3));
+            d[2][u >> 2] |= ((b >> 16) & 0xFFu) << (8 * (u & 3));
+          }
+      }
+#pragma unroll
+      for (int p = 0; p < 3; ++p)
+        *reinterpret_cast<uint4*>(Q8 + (((t * KB + kb) * 3 + p) * 1024 + 16 * lane)) =
+            make_uint4(d[p][0], d[p][1], d[p][2], d[p][3]);
+    }
+    S += __shfl_xor(S, 16, 64);
+    Nn += __shfl_xor(Nn, 16, 64);
+    S += __shfl_xor(S, 32, 64);
+    Nn += __shfl_xor(Nn, 32, 64);
+    if (g == 0) {
+      atomicAdd(&sS[j], (unsigned long long)S);
+      atomicAdd(&sN[j], (unsigned long long)Nn);
+    }
+    __syncthreads();
+    if (threadIdx.x < 16) {
+      const int64_t row = 16 * t + threadIdx.x;
+      const unsigned a2 = sM[threadIdx.x];
+      const int64_t Si = (int64_t)sS[threadIdx.x], Ni = (int64_t)sN[threadIdx.x];
+      double A = 0.0, B = 0.0, Sd = 0.0, okd = 0.0;
+      if (row < Q && a2 != 0u && a2 < 0x7F800000u) {  // Ni >= 2^44: the row maximum rounds to at least 2^22
+        B = 1.0 / sqrt((double)K * (double)Ni);
+        A = (double)Si * B;
+        Sd = (double)Si;
+        okd = 1.0;
+      }
+      double* o = st + 4 * row;
+      o[0] = A;
+      o[1] = B;
+      o[2] = Sd;
+      o[3] = okd;
+    }
+    __syncthreads();  // sM / sS / sN are cleared for the next tile
+  }
+}
+
+// The GEMM: k_cosq_t's structure (384 frames per 8-wave workgroup, wave w = frames 48 w .. + 47, frame fragments
+// straight from global memory one K step ahead, query fragments through two LDS stages, ping-pong between the two
+// waves of a SIMD, XCD-aware block order) with three query planes: 64 queries per workgroup, 4 query tiles x 3
+// planes = 12 fragments (12 KiB) per step and stage, 4 x 3 x 3 int32 accumulators of 4 = 144 VGPRs.  Waves 0-3
+// stage two fragments of a step (w and w + 8), waves 4-7 one.  Per K step and wave: 12 ds_read_b128, 1 or 2
+// ds_write_b128, 1 or 2 + 3 global loads of 1 KiB, 36 MFMAs.  EP 0: float64 score stores; EP 4: the staged top-k
+// epilogue of hq_cos_topk (cos_topk_row on the same slab layout, running-threshold hint included).
+template <int EP>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_cosqf_t(CosqArgs a, int64_t ftiles) {
+  constexpr int FT = 3, QT = kCosqfQ / 16, NP = 3, NF = QT * NP, TN = 8 * 16 * FT;
+  // the epilogue's stage (8 wave slices of 16 x 48 f64); during the K loop its first 24 KiB hold the two query stages
+  __shared__ __attribute__((aligned(16))) uint8_t smem[8 * 16 * 16 * FT * 8];
+  int8_t(*sA)[NF * 1024] = reinterpret_cast<int8_t(*)[NF * 1024]>(smem);
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int64_t blk = blockIdx.x;
+  const int64_t xcd = blk & 7, slot = blk >> 3;
+  const int qt = (int)(slot % a.c.qtiles);
+  const int64_t nt = xcd + 8 * (slot / a.c.qtiles);
+  if (nt >= a.c.ntiles) return;
+  const int KB = a.KB;
+  const int64_t qt0 = (int64_t)qt * QT;
+  // fragment f of a step = (query tile f / 3, plane f % 3); wave w stages f = w, waves 0-3 also f = w + 8
+  const bool two = __builtin_amdgcn_readfirstlane(wv) < NF - 8;
+  const int f1 = wv + 8;
+  const int8_t* srcA0 = a.A8 + ((qt0 + wv / NP) * KB * NP + wv % NP) * 1024 + 16 * lane;
+  const int8_t* srcA1 = a.A8 + ((qt0 + (two ? f1 / NP : 0)) * KB * NP + f1 % NP) * 1024 + 16 * lane;
+  const int8_t* srcB[FT];
+#pragma unroll
+  for (int j = 0; j < FT; ++j) {
+    int64_t t = nt * (TN / 16) + wv * FT + j;
+    if (t > ftiles - 1) t = ftiles - 1;  // the last frame tile may pass the padded rows
+    srcB[j] = a.B8 + t * KB * 1024 + 16 * lane;
+  }
+  i4v ra0, ra1 = i4v{0, 0, 0, 0};
+  i4v rb0[FT], rb1[FT];  // frame fragments of steps s, s + 1
+  auto loadA = [&](int kb) {
+    ra0 = *reinterpret_cast<const i4v*>(srcA0 + (int64_t)kb * (NP * 1024));
+    if (two) ra1 = *reinterpret_cast<const i4v*>(srcA1 + (int64_t)kb * (NP * 1024));
+  };
+  auto loadB = [&](int kb, i4v (&d)[FT]) {
+#pragma unroll
+    for (int j = 0; j < FT; ++j) d[j] = *reinterpret_cast<const i4v*>(srcB[j] + (int64_t)kb * 1024);
+  };
+  auto storeA = [&](int st) {
+    *reinterpret_cast<i4v*>(&sA[st][wv * 1024 + 16 * lane]) = ra0;
+    if (two) *reinterpret_cast<i4v*>(&sA[st][f1 * 1024 + 16 * lane]) = ra1;
+  };
+  i4v acc[QT][NP][FT];
+#pragma unroll
+  for (int i = 0; i < QT; ++i)
+#pragma unroll
+    for (int p = 0; p < NP; ++p)
+#pragma unroll
+      for (int j = 0; j < FT; ++j) acc[i][p][j] = i4v{0, 0, 0, 0};
+
+  // one K step, as k_cosq_t's
+  auto step = [&](int s, const i4v (&b)[FT], i4v (&nb)[FT]) {
+    const int st = s & 1;
+    storeA(st ^ 1);
+    loadA(s + 2 < KB ? s + 2 : KB - 1);
+    loadB(s + 1 < KB ? s + 1 : KB - 1, nb);
+    __builtin_amdgcn_sched_barrier(0);
+    i4v af[NF];
+#pragma unroll
+    for (int f = 0; f < NF; ++f) af[f] = *reinterpret_cast<const i4v*>(&sA[st][f * 1024 + 16 * lane]);
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < QT; ++i)
+#pragma unroll
+      for (int p = 0; p < NP; ++p)
+#pragma unroll
+        for (int j = 0; j < FT; ++j)
+          acc[i][p][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[NP * i + p], b[j], acc[i][p][j], 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_barrier" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+  };
+
+  loadA(0);
+  loadB(0, rb0);
+  storeA(0);
+  loadA(KB > 1 ? 1 : 0);
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  // ping-pong as in k_cos_t: group 1 (waves 4-7) one barrier phase behind, group 0 one extra barrier at the end
+  const int grp = __builtin_amdgcn_readfirstlane(wv >> 2);
+  if (grp) asm volatile("s_barrier" ::: "memory");
+  int s = 0;
+  for (; s + 2 <= KB; s += 2) {
+    step(s, rb0, rb1);
+    step(s + 1, rb1, rb0);
+  }
+  if (s < KB) step(s, rb0, rb1);
+  if (!grp) asm volatile("s_barrier" ::: "memory");
+  // epilogue: lane holds queries 16 i + 4 (lane >> 4) + r, frames 16 j + (lane & 15) of its wave's columns; sa
+  // covers the padded query rows, a frame column past the padded frame rows is clamped for the load, never stored
+  const int64_t q0 = qt0 * 16, n0 = nt * TN + (int64_t)wv * 16 * FT;
+  const int64_t nrows = ftiles * 16;
+  const int64_t Ki = a.K;
+  double Ac[FT], Bc[FT], okc[FT];
+  int64_t Sc[FT];
+#pragma unroll
+  for (int j = 0; j < FT; ++j) {
+    const int64_t n = n0 + 16 * j + (lane & 15);
+    const double4 c = *reinterpret_cast<const double4*>(a.sb + 4 * (n < nrows ? n : nrows - 1));
+    Ac[j] = c.x;
+    Bc[j] = c.y;
+    Sc[j] = (int64_t)c.z;
+    okc[j] = c.w;
+  }
+  double* stage = reinterpret_cast<double*>(smem) + wv * 16 * 16 * FT;
+#pragma unroll
+  for (int i = 0; i < QT; ++i) {
+    const int64_t qb = q0 + 16 * i + 4 * (lane >> 4);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int64_t q = qb + r;
+      const double4 sq = *reinterpret_cast<const double4*>(a.sa + 4 * q);
+      const int64_t Sv = (int64_t)sq.z;
+#pragma unroll
+      for (int j = 0; j < FT; ++j) {
+        const int64_t n = n0 + 16 * j + (lane & 15);
+        const double v = cosqf_score(acc[i][0][j][r], acc[i][1][j][r], acc[i][2][j][r], Ki, sq.x, sq.y, Sv, sq.w,
+                                     Ac[j], Bc[j], Sc[j], okc[j]);
+        if constexpr (EP == 4) {  // top-k: every value is staged, rows and columns are masked in cos_topk_row
+          stage[(4 * (lane >> 4) + r) * 16 * FT + 16 * j + (lane & 15)] = v;
+        } else if (q < a.c.Q && n < a.c.N) {
+          __builtin_nontemporal_store(v, a.c.out + q * a.c.N + n);  // write-once scores
+        }
+      }
+    }
+    if constexpr (EP == 4) {
+      // as k_cos_t's EP 4: wave w selects for queries 2 w and 2 w + 1 of the row block; every wave of the
+      // workgroup reaches both barriers of every row block
+      __syncthreads();
+#pragma unroll 1
+      for (int h = 0; h < 2; ++h) {
+        const int row = 2 * wv + h;
+        const int64_t q = q0 + 16 * i + row;
+        if (q < a.c.Q) cos_topk_row<TN>(reinterpret_cast<const double*>(smem), row, q, nt, a.c);
+      }
+      __syncthreads();  // the next row block overwrites the stage
+    }
+  }
+}
+
+template <int EP>
+static int launch_cosqf(CosqArgs a, hipStream_t s) {
+  const int64_t np_rows = hq_cosq_padded_rows(a.c.N);
+  a.c.qtiles = (int)(hq_cosqf_padded_rows(a.c.Q) / kCosqfQ);
+  a.c.ntiles = (np_rows + 383) / 384;
+  const int64_t nt8 = ((a.c.ntiles + 7) / 8) * 8;
+  const int64_t blocks = nt8 * a.c.qtiles;
+  if (blocks > 0x7FFFFFFF) return fail(HQ_E_UNSUPPORTED, "too many tiles");
+  hipLaunchKernelGGL(k_cosqf_t<EP>, dim3((unsigned)blocks), dim3(512), 0, s, a, np_rows / 16);
+  HQ_CHECK_LAUNCH();
+  return HQ_OK;
+}
+
+}  // namespace hq
+
+extern "C" {
+
+int64_t hq_cosqf_padded_rows(int64_t Q) { return Q <= 0 ? 0 : ((Q + kCosqfQ - 1) / kCosqfQ) * kCosqfQ; }
+
+int hq_cosqf_prepare(const float* X, int64_t Q, int64_t ld, int K, void* Q8, double* stats, hq_stream_t stream) {
+  if (Q < 0 || K <= 0 || ld < K) return fail(HQ_E_INVALID, "bad shape Q=%lld K=%d ld=%lld", (long long)Q, K, (long long)ld);
+  if (Q == 0) return HQ_OK;
+  if (K > kCosqMaxK) return fail(HQ_E_UNSUPPORTED, "K=%d: the int32 accumulators hold K <= %d", K, kCosqMaxK);
+  if (!X || !Q8 || !stats) return fail(HQ_E_INVALID, "null buffer");
+  const int64_t rows = hq_cosqf_padded_rows(Q);
+  int64_t blocks = rows / 16;
+  if (blocks > 65536) blocks = 65536;
+  const int fast = ((uintptr_t)X % 16 == 0 && ld % 4 == 0) ? 1 : 0;
+  hipLaunchKernelGGL(k_cosqf_prepare, dim3((unsigned)blocks), dim3(1024), 0, (hipStream_t)stream, X, Q, ld, K,
+                     hq_cosq_padded_k(K) / kCosqK, rows, reinterpret_cast<int8_t*>(Q8), stats, fast);
+  HQ_CHECK_LAUNCH();
+  return HQ_OK;
+}
+
+int hq_cosqf_scores(const void* Q8, const double* stats_q, int Q, const void* B8, const double* stats_b, int64_t N, int K,
+                    double* out, hq_stream_t stream) {
+  if (Q < 0 || N < 0 || K <= 0) return fail(HQ_E_INVALID, "bad shape Q=%d N=%lld K=%d", Q, (long long)N, K);
+  if (Q == 0 || N == 0) return HQ_OK;
+  if (K > kCosqMaxK) return fail(HQ_E_UNSUPPORTED, "K=%d: the int32 accumulators hold K <= %d", K, kCosqMaxK);
+  if (!Q8 || !stats_q || !B8 || !stats_b || !out) return fail(HQ_E_INVALID, "null buffer");
+  CosqArgs a = cosq_args(Q8, stats_q, Q, B8, stats_b, N, K);
+  a.c.out = out;
+  return launch_cosqf<0>(a, (hipStream_t)stream);
+}
+
+// Workspace layout and merge stage: hq_cos_topk's, as hq_cosq_topk.
+size_t hq_cosqf_topk_workspace_size(int Q, int64_t N, int k) { return hq_cos_topk_workspace_size(Q, N, k); }
+
+int hq_cosqf_topk(const void* Q8, const double* stats_q, int Q, const void* B8, const double* stats_b, int64_t N, int K,
+                  int k, double threshold, int thr_mode, int64_t id_base, void* workspace, size_t workspace_bytes,
+                  double* out_score, int64_t* out_id, hq_stream_t stream) {
+  if (Q < 0 || N < 0 || K <= 0 || k < 1) return fail(HQ_E_INVALID, "bad shape Q=%d N=%lld K=%d k=%d", Q, (long long)N, K, k);
+  if (Q == 0 || N == 0) return HQ_OK;
+  if (k > 64) return fail(HQ_E_UNSUPPORTED, "k=%d: the fused frame top-k keeps lists of at most 64", k);
+  if (K > kCosqMaxK) return fail(HQ_E_UNSUPPORTED, "K=%d: the int32 accumulators hold K <= %d", K, kCosqMaxK);
+  if (!Q8 || !stats_q || !B8 || !stats_b || !workspace || !out_score || !out_id) return fail(HQ_E_INVALID, "null buffer");
+  if (workspace_bytes < hq_cosqf_topk_workspace_size(Q, N, k)) return fail(HQ_E_INVALID, "workspace too small");
+  const hipStream_t s = (hipStream_t)stream;
+  const int64_t P = cos_topk_tiles(N);
+  uint8_t* w = reinterpret_cast<uint8_t*>(workspace);
+  auto take = [&](size_t bytes) { uint8_t* p = w; w += cos_topk_al(bytes); return p; };
+  uint64_t* hint = reinterpret_cast<uint64_t*>(take((size_t)Q * 8));
+  double* bs[3];
+  int64_t* bi[3];
+  int64_t cap = P;  // lists per query a buffer holds: P, ceil(P / 64), ceil(P / 4096)
+  for (int i = 0; i < 3; ++i) {
+    bs[i] = reinterpret_cast<double*>(take((size_t)Q * cap * k * 8));
+    bi[i] = reinterpret_cast<int64_t*>(take((size_t)Q * cap * k * 8));
+    cap = (cap + 63) / 64;
+  }
+  CosqArgs a = cosq_args(Q8, stats_q, Q, B8, stats_b, N, K);
+  a.c.tk_s = bs[0];
+  a.c.tk_id = bi[0];
+  a.c.tk_hint = opt(OPT_COS_TOPK_HINT, 1) ? hint : nullptr;
+  a.c.tk_thr = threshold;
+  a.c.tk_mode = thr_mode;
+  a.c.tk_k = k;
+  if (a.c.tk_hint) HQ_CHECK_HIP(hipMemsetAsync(hint, 0, (size_t)Q * 8, s));
+  const int rc = launch_cosqf<4>(a, s);
   if (rc != HQ_OK) return rc;
   int64_t Pc = P;
   int cur = 0;

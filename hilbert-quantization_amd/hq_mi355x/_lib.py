@@ -127,6 +127,11 @@ SIGNATURES = {
     "hq_cosq_scores": (_i, [_p, _p, _i, _p, _p, _i64, _i, _p, _p]),
     "hq_cosq_topk_workspace_size": (_sz, [_i, _i64, _i]),
     "hq_cosq_topk": (_i, [_p, _p, _i, _p, _p, _i64, _i, _i, _d, _i, _i64, _p, _sz, _p, _p, _p]),
+    "hq_cosqf_padded_rows": (_i64, [_i64]),
+    "hq_cosqf_prepare": (_i, [_p, _i64, _i64, _i, _p, _p, _p]),
+    "hq_cosqf_scores": (_i, [_p, _p, _i, _p, _p, _i64, _i, _p, _p]),
+    "hq_cosqf_topk_workspace_size": (_sz, [_i, _i64, _i]),
+    "hq_cosqf_topk": (_i, [_p, _p, _i, _p, _p, _i64, _i, _i, _d, _i, _i64, _p, _sz, _p, _p, _p]),
 }
 
 _lock = threading.Lock()

@@ -1193,3 +1193,111 @@ def cosq_topk(q: CosQRows, c: CosQRows, k: int, threshold: float = 0.0, thr_mode
         _chk(_L().hq_cosq_topk(ptr(b.X8), ptr(b.stats), b.N, ptr(c.X8), ptr(c.stats), N, q.K, k, float(threshold),
                                int(thr_mode), int(id_base), ptr(ws), wb, ptr(os_[q0:q1]), ptr(oi[q0:q1]), stream()), exc)
     return os_, oi
+
+
+# ------------------------------------------------ float32 queries against the u8 frame store (exact, asymmetric)
+
+
+class CosQFRows:
+    """Float32 query rows prepared for the asymmetric cosine against CosQRows frames (hq_cosqf_prepare): Q8
+    [Qp, 3 Kp] the three int8 digit planes of the rows' 24-bit fixed-point values in i8 MFMA operand fragments,
+    stats [Qp, 4] f64 (A_q, B_q, Sv, ok)."""
+
+    __slots__ = ("Q8", "stats", "N", "K")
+
+    def __init__(self, Q8, stats, N, K):
+        self.Q8, self.stats, self.N, self.K = Q8, stats, int(N), int(K)
+
+    @property
+    def nbytes(self) -> int:
+        return self.Q8.numel() * self.Q8.element_size() + self.stats.numel() * self.stats.element_size()
+
+
+def cosqf_prepare(x, rows: Optional[int] = None, exc=None) -> CosQFRows:
+    """float32 frames [Q, r, c] (or rows [Q, K]) -> CosQFRows of the first `rows` rows of every frame (all of them
+    by default).  The frames are read in place: K = rows * c floats out of every r * c."""
+    t = torch()
+    if x.dtype != t.float32:
+        raise TypeError("cosqf_prepare expects float32 queries (u8 query frames go through cosq_prepare)")
+    if x.dim() < 2:
+        raise ValueError("queries must be [Q, ...]")
+    Q = int(x.shape[0])
+    if x.dim() == 2:
+        if rows is not None:
+            raise ValueError("rows= needs frames [Q, r, c]")
+        x2 = x if x.stride(-1) == 1 else x.contiguous()
+        K = int(x2.shape[1])
+    else:
+        r, c = int(x.shape[1]), int(np.prod(x.shape[2:]))
+        rows = r if rows is None else int(rows)
+        if not 1 <= rows <= r:
+            raise ValueError(f"rows = {rows} of {r}")
+        x2 = _contig(x).view(Q, r * c)
+        K = rows * c
+    Kp = int(_L().hq_cosq_padded_k(K))
+    Qp = int(_L().hq_cosqf_padded_rows(Q))
+    Q8 = t.empty((max(Qp, 1), 3 * max(Kp, 1)), dtype=t.int8, device=x2.device)
+    stats = t.empty((max(Qp, 1), 4), dtype=t.float64, device=x2.device)
+    if Q:
+        _chk(_L().hq_cosqf_prepare(ptr(x2), Q, x2.stride(0) if Q > 1 else int(x2.shape[1]), K, ptr(Q8), ptr(stats),
+                                   stream()), exc)
+    return CosQFRows(Q8, stats, Q, K)
+
+
+def cosqf_scores(q: CosQFRows, c: CosQRows, exc=None):
+    """(cos + 1) / 2 of every prepared float32 query (its 24-bit fixed-point row) against every dequantised
+    prepared frame -> f64 [Q, N], within a few float64 roundings of the exact value (hq_cosqf_scores: three exact
+    int8 MFMA contractions per pair)."""
+    t = torch()
+    if q.K != c.K:
+        raise ValueError(f"query length {q.K} != frame length {c.K}")
+    out = t.empty((q.N, c.N), dtype=t.float64, device=q.Q8.device)
+    _chk(_L().hq_cosqf_scores(ptr(q.Q8), ptr(q.stats), q.N, ptr(c.X8), ptr(c.stats), c.N, q.K, ptr(out), stream()), exc)
+    return out
+
+
+def _cosqf_query_block(q: CosQFRows, q0: int, q1: int) -> CosQFRows:
+    """Prepared queries [q0, q1), q0 a multiple of 16 (fragments are tile-major: a block is a pointer offset)."""
+    return q if (q0 == 0 and q1 == q.N) else CosQFRows(q.Q8[q0:], q.stats[q0:], q1 - q0, q.K)
+
+
+def cosqf_topk(q: CosQFRows, c: CosQRows, k: int, threshold: float = 0.0, thr_mode: int = 0, id_base: int = 0,
+               workspace_limit: int = 256 << 20, exc=None):
+    """The k nearest prepared u8 frames of every prepared float32 query -> (scores [Q, k] f64, ids [Q, k] i64),
+    equal to select_topk(cosqf_scores(q, c), k, threshold, thr_mode, id_base) in ids, order and score bits
+    (hq_cosqf_topk).  Workspace, query blocks under workspace_limit and the dense route for k > 64 or k > N: as
+    cosq_topk."""
+    t = torch()
+    if q.K != c.K:
+        raise ValueError(f"query length {q.K} != frame length {c.K}")
+    k, Q, N = int(k), q.N, c.N
+    if k < 1:
+        raise ValueError(f"k = {k}")
+    dev = q.Q8.device
+    os_ = t.full((Q, k), float("-inf"), dtype=t.float64, device=dev)
+    oi = t.full((Q, k), -1, dtype=t.int64, device=dev)
+    if Q == 0 or N == 0:
+        return os_, oi
+    limit = max(int(workspace_limit), 1)
+    if k > 64 or k > N:
+        per = max(128, limit // (8 * N) // 128 * 128)
+        for q0 in range(0, Q, per):
+            q1 = min(Q, q0 + per)
+            s, i, _, _ = select_topk(cosqf_scores(_cosqf_query_block(q, q0, q1), c, exc), k, threshold, thr_mode,
+                                     id_base, exc)
+            os_[q0:q1], oi[q0:q1] = s, i
+        return os_, oi
+    size = _L().hq_cosqf_topk_workspace_size
+    per = Q
+    if int(size(Q, N, k)) > limit:
+        per = max(128, limit // max(int(size(128, N, k)), 1) * 128)
+        while per > 128 and int(size(per, N, k)) > limit:
+            per -= 128
+    for q0 in range(0, Q, per):
+        q1 = min(Q, q0 + per)
+        b = _cosqf_query_block(q, q0, q1)
+        wb = int(size(b.N, N, k))
+        ws = _workspace(wb, dev)
+        _chk(_L().hq_cosqf_topk(ptr(b.Q8), ptr(b.stats), b.N, ptr(c.X8), ptr(c.stats), N, q.K, k, float(threshold),
+                                int(thr_mode), int(id_base), ptr(ws), wb, ptr(os_[q0:q1]), ptr(oi[q0:q1]), stream()), exc)
+    return os_, oi

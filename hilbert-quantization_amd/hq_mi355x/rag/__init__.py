@@ -1,4 +1,7 @@
-"""RAG-side components (hilbert_quantization.rag.*) backed by libhq_mi355x."""
+"""RAG-side components (hilbert_quantization.rag.*) backed by libhq_mi355x.
+
+QuantizedFrameCorpus searches the store's u8 frames in place with u8 queries (search, search_parameters) and with
+float32 queries at full precision (search_float, search_parameters(quantize_query=False))."""
 from .hilbert_mapper import HilbertCurveMapperImpl
 from .hierarchical_index_generator import HierarchicalIndexGenerator
 from .similarity import (FrameCosineCorpus, QuantizedFrameCorpus, apply_progressive_threshold,

@@ -2,7 +2,8 @@
 604-714, 1025-1138.
 
 Every score runs on the GPU (hq_cosine_scores / hq_cosine_scores_dt / hq_cos_scores_mfma, hq_cos_topk for
-rankings of large float32 problems, hq_spatial_locality, hq_detect_heights, hq_threshold_select); the level weights and the progressive
+rankings of large float32 problems, hq_cosq_topk / hq_cosqf_topk for u8 / float32 queries against the u8 frame
+store, hq_spatial_locality, hq_detect_heights, hq_threshold_select); the level weights and the progressive
 thresholds are host-side constants computed with the reference's own Python float expressions.  Inputs
 keep their dtype: float64 arrays are scored in float64 (the reference's np.dot / np.linalg.norm run in
 the input dtype), float32 ones from float32 values."""
@@ -95,10 +96,13 @@ class QuantizedFrameCorpus:
     (mn, mx) is not finite scores 0.0.  `rows` is how many leading rows of every frame are compared: by default
     c when r == c + 1 (the pipeline's frames, index row left out), else r.  rows * c <= 65536.
 
-    Queries must be u8 frames with their own (min, max) too: search() takes them as they are,
-    search_parameters() quantises float32 parameters with map_index_quantize at the corpus's n first.  Float32
-    query frames against a u8 corpus without quantising them are out of scope (FrameCosineCorpus does that on
-    decoded frames)."""
+    Two kinds of query meet the same resident corpus.  u8 frames with their own (min, max): search() takes them
+    as they are, search_parameters() quantises float32 parameters with map_index_quantize at the corpus's n first.
+    Float32 frames at full precision: search_float() (hq_cosqf_*: the query as three int8 digit planes of its
+    24-bit fixed-point row, the same exact integer contraction), search_parameters(quantize_query=False) for
+    float32 parameters; those scores are cosines of the query itself to 2^-23 sqrt(K) amax / |q| (below 7e-7 for
+    gaussian rows), not of its 8-bit quantisation.  Queries of any other dtype (float64, float16) are out of scope:
+    convert them to float32 first."""
 
     def __init__(self, frames_u8, minmax, rows=None):
         t = torch()
@@ -145,8 +149,35 @@ class QuantizedFrameCorpus:
         thr, mode = _threshold_mode(threshold)
         return K.cosq_topk(K.cosq_prepare(q, to_dev(query_minmax), self.rows), self._rows, int(k), thr, mode)
 
-    def search_parameters(self, x, k: int = 10, threshold=None):
-        """Float32 parameters [Q, d]: quantised like the store (map_index_quantize at n = c), then search()."""
+    def search_float(self, query_frames_f32, k: int = 10, threshold=None):
+        """float32 query frames [Q, r, c] (or one [r, c]; r >= the corpus's rows, same c), or rows [Q, K] with K =
+        the corpus's K, kept at full precision -> device (scores [Q, k] f64, ids [Q, k] i64) as search() orders and
+        pads them.  A zero row and a row holding a NaN or inf score 0.0 against every frame."""
+        t = torch()
+        q = to_dev(query_frames_f32)
+        if q.dtype != t.float32:
+            raise TypeError("search_float expects float32 queries (u8 query frames go through search())")
+        thr, mode = _threshold_mode(threshold)
+        if q.dim() == 2 and int(q.shape[1]) == self.K and int(q.shape[1]) != self.shape[1]:
+            return K.cosqf_topk(K.cosqf_prepare(q), self._rows, int(k), thr, mode)
+        if q.dim() == 2:
+            q = q.unsqueeze(0)
+        if q.dim() != 3 or int(q.shape[2]) != self.shape[1] or int(q.shape[1]) < self.rows:
+            raise ValueError(f"query frames {tuple(q.shape)} do not hold {self.rows} rows of {self.shape[1]}")
+        return K.cosqf_topk(K.cosqf_prepare(q, self.rows), self._rows, int(k), thr, mode)
+
+    def search_parameters(self, x, k: int = 10, threshold=None, quantize_query: bool = True):
+        """Float32 parameters [Q, d]: quantised like the store (map_index_quantize at n = c), then search().
+        quantize_query=False keeps the query's precision: the parameters are laid onto n x n along the curve
+        (map_to_2d, zero padded as the pipeline pads) and go through search_float()."""
+        if not quantize_query:
+            t = torch()
+            n = self.shape[1]
+            p = to_dev(x)
+            if p.dtype != t.float32:
+                raise TypeError("search_parameters(quantize_query=False) expects float32 parameters")
+            p2 = p.reshape(1, -1) if p.dim() == 1 else p
+            return self.search_float(K.map_to_2d(p2[:, :n * n], n), k, threshold)
         frames, _, mm = K.map_index_quantize(to_dev(x), self.shape[1], want_idx=False)
         return self.search(frames, mm, k, threshold)
 

@@ -591,8 +591,9 @@ int hq_cos_topk(const void* A16, const double* inv_a, int Q, const void* B16, co
 /* ---- compressed-domain frame search: exact cosine top-k on u8 frames ------------------------------
  * The store's own format (hq_map_index_quantize / hq_quantize_u8: K bytes u and float32 (mn, mx) per frame,
  * x_i = mn + (mx - mn) u_i / 255) is searched without decoding: the cosine of two dequantised frames is a
- * closed form of exact integers and the two (mn, mx) pairs.  Queries must be u8 rows too (quantise them with
- * hq_map_index_quantize / hq_quantize_u8); float32 queries against a u8 corpus are not offered.
+ * closed form of exact integers and the two (mn, mx) pairs.  Queries of hq_cosq_* are u8 rows too (quantise them
+ * with hq_map_index_quantize / hq_quantize_u8); float32 queries against the same prepared corpus, without
+ * quantising them to 8 bits, go through hq_cosqf_* below.
  * The contract, everything in float64 from the float32 (mn, mx):
  *   row:  w_i = u_i - 128;  S = sum w_i, T = sum w_i^2 (exact integers);  s = (mx - mn) / 255 (0 when mx == mn);
  *         m = mn + s (128 + S / K) (the row mean);  V = K T - S^2 (exact in int64, >= 0);  n^2 = K m^2 + s^2 V / K;
@@ -629,6 +630,59 @@ int hq_cosq_topk(const void* A8, const double* stats_a, int Q, const void* B8, c
                  int K, int k, double threshold, int thr_mode, int64_t id_base,
                  void* workspace, size_t workspace_bytes,
                  double* out_score, int64_t* out_id, hq_stream_t stream);
+
+/* ---- float32 queries against the u8 frame store: exact asymmetric cosine top-k --------------------
+ * The corpus stays compressed (exactly what hq_cosq_prepare wrote: one resident corpus serves both query kinds),
+ * the query keeps its float32 precision: a query row is rounded to 24-bit fixed point, stored as three int8 digit
+ * planes, and every plane is contracted exactly with the corpus's signed bytes by v_mfma_i32_16x16x64_i8.
+ * The contract:
+ *   query row: K float32 values q_i (ld floats between rows, ld >= K).
+ *         amax = max |q_i|.  If amax == 0, or any q_i is NaN or inf, the row has ok = 0: it scores 0.0 against
+ *         every frame and changes no other score.
+ *         e: amax = f 2^e with f in [0.5, 1) (frexp).
+ *         v_i = clamp(rint(q_i 2^(23 - e)), -2^23, 2^23 - 1), rint = round to nearest even, the scaling exact (ldexp,
+ *         or in float64: 2^(23 - e) itself overflows float32 for subnormal rows).  The clamp only ever acts on
+ *         +2^23.  v is an integer vector; subnormal rows and rows up to FLT_MAX are in the domain.
+ *         Sv = sum v_i, Nv = sum v_i^2: exact int64 values (|Sv| < 2^39, Nv < 2^62).
+ *         B_q = 1 / sqrt(K Nv), A_q = Sv B_q, in float64.
+ *   pair: D = sum v_i w_i with w = u - 128, exact, from three int32 accumulators of int8 digit planes of v against
+ *         the corpus's signed bytes.  Digits here: bytes 1 and 0 of the two's-complement v with the top bit flipped
+ *         (b - 128), byte 2 as it is, so D = 65536 P2 + 256 P1 + P0 + 32896 S_c, |P_j| <= 2^30 for K <= 65536 (the
+ *         encoding is the implementation's choice; the definition of v is not).
+ *         t = K D - Sv S_c, the exact integer (|t| <= 2^62, each term up to 2^62: 64-bit integer arithmetic, since
+ *         float64 products round both terms past 2^53 before they cancel; on a frame of one 255 among zeros and a
+ *         same-sign query at K = 65536 the float64 t is off by several units, which moves a score by 1e-15, and by
+ *         up to 2.4e-13 on a frame of one 1 among zeros), converted to float64 once.
+ *         cos = A_q A_c + (B_q B_c) t with the (A_c, B_c, S_c, ok_c) hq_cosq_prepare stores;
+ *         score = (cos + 1) / 2, and 0.0 when either ok is 0.
+ *   The epilogues are compiled with -ffp-contract=off and use one pair function, so the dense and the fused
+ *   route agree bit for bit.  Limits: 1 <= K <= 65536 (larger: HQ_E_UNSUPPORTED), 1 <= k <= 64 in hq_cosqf_topk.
+ *   What the score means: it is the cosine of (v, dequantised frame) to a few float64 roundings (a NumPy model of
+ *   the formula stays within 3e-16 of the long-double value over K = 1 .. 65536; 1e-13 is tested).  Against the
+ *   query's own float32 values, |delta score| <= 2^(e-24) sqrt(K) / |q|: the per-element rounding is at most
+ *   2^(e-24), and with 2^e <= 2 amax that is at most 2^-23 sqrt(K) amax / |q| -- below 7e-7 for gaussian and
+ *   post-ReLU rows at any K (amax / |q| about 4 / sqrt(K)); the worst adversarial row found reached 3.2e-6 at
+ *   K = 65536.
+ * hq_cosqf_prepare: X f32 [Q, K] (ld floats between rows) -> Q8: hq_cosqf_padded_rows(Q) x hq_cosq_padded_k(K) x 3
+ *   bytes, the three digit planes in the corpus's fragment layout (16-row tile t, K step kb of 64, plane p: the
+ *   1 KiB fragment at ((t KB + kb) 3 + p) 1024; lane 16 g + j = row 16 t + j, bytes 64 kb + 16 g .. + 15; a step's
+ *   query operands are one contiguous 3 KiB), pad rows and pad K positions 0, and stats f64 [padded rows, 4] =
+ *   (A_q, B_q, Sv, ok).  One launch, no host round trip.  16-byte loads when the base is a multiple of 16 bytes and
+ *   ld a multiple of 4 floats, element loads otherwise.
+ * hq_cosqf_scores: out [Q, N] f64, the dense scores.  B8 / stats_b: hq_cosq_prepare's outputs.
+ * hq_cosqf_topk: arguments and semantics of hq_cosq_topk (threshold, thr_mode 0 / 1 / 2, id_base, -inf / -1
+ *   padding, 1 <= k <= 64 else HQ_E_UNSUPPORTED, (score descending, id ascending)); the lists equal
+ *   hq_select_topk_ws of hq_cosqf_scores bit for bit.  workspace: hq_cosqf_topk_workspace_size(Q, N, k) bytes.
+ * Zero Q or N: HQ_OK before any pointer is looked at; negative sizes, K < 1, ld < K, NULL operands: HQ_E_INVALID. */
+int64_t hq_cosqf_padded_rows(int64_t Q);
+int hq_cosqf_prepare(const float* X, int64_t Q, int64_t ld, int K, void* Q8, double* stats, hq_stream_t stream);
+int hq_cosqf_scores(const void* Q8, const double* stats_q, int Q, const void* B8, const double* stats_b, int64_t N,
+                    int K, double* out, hq_stream_t stream);
+size_t hq_cosqf_topk_workspace_size(int Q, int64_t N, int k);
+int hq_cosqf_topk(const void* Q8, const double* stats_q, int Q, const void* B8, const double* stats_b, int64_t N,
+                  int K, int k, double threshold, int thr_mode, int64_t id_base,
+                  void* workspace, size_t workspace_bytes,
+                  double* out_score, int64_t* out_id, hq_stream_t stream);
 
 /* ---- S7: the rest of the RAG scorer (rag/search/engine.py) --------------------------------------
  * hq_cosine_scores_dt: as hq_cosine_scores for float32 (HQ_F32) or float64 (HQ_F64) rows; float64
