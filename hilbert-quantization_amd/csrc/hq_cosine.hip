@@ -34,7 +34,9 @@
 // Compressed-domain search (hq_cosq_*; the section before the last of this file): the same tile, ping-pong,
 // top-k epilogue and merge on the store's own u8 frames + (min, max), contracted exactly by v_mfma_i32_16x16x64_i8.
 // Float32 queries against that u8 corpus (hq_cosqf_*; the last section): the query as three int8
-// digit planes of a 24-bit fixed-point row, three exact int32 sums per pair, the same epilogue pieces.
+// digit planes of a 24-bit fixed-point row, three exact int32 sums per pair, the same epilogue pieces.  Both int8
+// routes run one GEMM template, k_cosq_t<NP, EP> (NP query planes), and all three fused routes one host driver
+// (cos_topk_run).
 #include "hq_common.h"
 
 #include <stdlib.h>
@@ -1007,32 +1009,40 @@ int hq_cos_scores_mfma(const void* A16, const double* inv_a, int Q, const void* 
   return launch_t<3, 1, 1>(a, (hipStream_t)stream);
 }
 
+}  // extern "C"
+
 // ---- fused top-k ---------------------------------------------------------------------------------------
 // Workspace of hq_cos_topk: [Q] hint keys, the stage-1 slab [Q, P, k] (f64 scores, i64 frames; P = frame
 // tiles of 384) and two merge buffers [Q, ceil(P / 64), k], [Q, ceil(P / 4096), k]; every piece 256-aligned.
+// hq_cosq_topk and hq_cosqf_topk use the same layout, checks and driver around their own first stage.
+namespace hq {
+
 static int64_t cos_topk_tiles(int64_t N) { return (hq_cos_padded_rows(N) + 383) / 384; }
 static size_t cos_topk_al(size_t b) { return (b + 255) & ~(size_t)255; }
 
-size_t hq_cos_topk_workspace_size(int Q, int64_t N, int k) {
-  if (Q <= 0 || N <= 0 || k <= 0) return 0;
-  const size_t P = (size_t)cos_topk_tiles(N), P1 = (P + 63) / 64, P2 = (P1 + 63) / 64;
-  return cos_topk_al((size_t)Q * 8) + 2 * cos_topk_al((size_t)Q * P * k * 8) + 2 * cos_topk_al((size_t)Q * P1 * k * 8) +
-         2 * cos_topk_al((size_t)Q * P2 * k * 8);
-}
-
-int hq_cos_topk(const void* A16, const double* inv_a, int Q, const void* B16, const double* inv_b, int64_t N, int K,
-                int k, double threshold, int thr_mode, int64_t id_base, void* workspace, size_t workspace_bytes,
-                double* out_score, int64_t* out_id, hq_stream_t stream) {
+// The argument checks the three fused routes share, in the order that decides which error wins: shape, empty
+// problem (HQ_OK, *run stays false), k, the route's own limit (route(), HQ_OK to go on), buffers, workspace.
+template <class Route>
+static int cos_topk_check(int Q, int64_t N, int K, int k, bool buffers, size_t workspace_bytes, bool* run,
+                          Route route) {
+  *run = false;
   if (Q < 0 || N < 0 || K <= 0 || k < 1) return fail(HQ_E_INVALID, "bad shape Q=%d N=%lld K=%d k=%d", Q, (long long)N, K, k);
   if (Q == 0 || N == 0) return HQ_OK;
   if (k > 64) return fail(HQ_E_UNSUPPORTED, "k=%d: the fused frame top-k keeps lists of at most 64", k);
-  const int64_t ek = opt(OPT_COS_KERNEL, 0);
-  if (ek >= 1 && ek <= 3)
-    return fail(HQ_E_UNSUPPORTED, "cos_kernel=%lld prepares the row-major layout; the fused frame top-k needs the tiled one",
-                (long long)ek);
-  if (!A16 || !inv_a || !B16 || !inv_b || !workspace || !out_score || !out_id) return fail(HQ_E_INVALID, "null buffer");
+  const int rc = route();
+  if (rc != HQ_OK) return rc;
+  if (!buffers) return fail(HQ_E_INVALID, "null buffer");
   if (workspace_bytes < hq_cos_topk_workspace_size(Q, N, k)) return fail(HQ_E_INVALID, "workspace too small");
-  const hipStream_t s = (hipStream_t)stream;
+  *run = true;
+  return HQ_OK;
+}
+
+// The fused top-k around a route's first stage: carve the workspace, point tk's top-k fields at the hint and the
+// stage-1 slab, zero the hint, launch() the GEMM whose epilogue fills the slab (the caller's lambda reads tk),
+// then merge 64 lists at a time until one is left: slab -> buffer 1 -> buffer 2 -> buffer 1 ...
+template <class Launch>
+static int cos_topk_run(int Q, int64_t N, int k, double threshold, int thr_mode, int64_t id_base, void* workspace,
+                        double* out_score, int64_t* out_id, hipStream_t s, CosArgs& tk, Launch launch) {
   const int64_t P = cos_topk_tiles(N);
   uint8_t* w = reinterpret_cast<uint8_t*>(workspace);
   auto take = [&](size_t bytes) { uint8_t* p = w; w += cos_topk_al(bytes); return p; };
@@ -1045,27 +1055,15 @@ int hq_cos_topk(const void* A16, const double* inv_a, int Q, const void* B16, co
     bi[i] = reinterpret_cast<int64_t*>(take((size_t)Q * cap * k * 8));
     cap = (cap + 63) / 64;
   }
-  CosArgs a;
-  a.A = reinterpret_cast<const _Float16*>(A16);
-  a.B = reinterpret_cast<const _Float16*>(B16);
-  a.ia = inv_a;
-  a.ib = inv_b;
-  a.Q = Q;
-  a.N = N;
-  a.Kp = hq_cos_padded_k(K);
-  a.ntiles = hq_cos_padded_rows(N) / kCosT;
-  a.out = nullptr;
-  a.outf = nullptr;
-  a.tk_s = bs[0];
-  a.tk_id = bi[0];
-  a.tk_hint = opt(OPT_COS_TOPK_HINT, 1) ? hint : nullptr;
-  a.tk_thr = threshold;
-  a.tk_mode = thr_mode;
-  a.tk_k = k;
-  if (a.tk_hint) HQ_CHECK_HIP(hipMemsetAsync(hint, 0, (size_t)Q * 8, s));
-  const int rc = launch_t<3, 1, 1, 4>(a, s);  // the default kernel's K loop, top-k epilogue
+  tk.tk_s = bs[0];
+  tk.tk_id = bi[0];
+  tk.tk_hint = opt(OPT_COS_TOPK_HINT, 1) ? hint : nullptr;
+  tk.tk_thr = threshold;
+  tk.tk_mode = thr_mode;
+  tk.tk_k = k;
+  if (tk.tk_hint) HQ_CHECK_HIP(hipMemsetAsync(hint, 0, (size_t)Q * 8, s));
+  const int rc = launch();
   if (rc != HQ_OK) return rc;
-  // merge 64 lists at a time until one is left: slab -> buffer 1 -> buffer 2 -> buffer 1 ...
   int64_t Pc = P;
   int cur = 0;
   for (;;) {
@@ -1081,6 +1079,47 @@ int hq_cos_topk(const void* A16, const double* inv_a, int Q, const void* B16, co
     cur = nxt;
   }
   return HQ_OK;
+}
+
+}  // namespace hq
+
+extern "C" {
+
+size_t hq_cos_topk_workspace_size(int Q, int64_t N, int k) {
+  if (Q <= 0 || N <= 0 || k <= 0) return 0;
+  const size_t P = (size_t)cos_topk_tiles(N), P1 = (P + 63) / 64, P2 = (P1 + 63) / 64;
+  return cos_topk_al((size_t)Q * 8) + 2 * cos_topk_al((size_t)Q * P * k * 8) + 2 * cos_topk_al((size_t)Q * P1 * k * 8) +
+         2 * cos_topk_al((size_t)Q * P2 * k * 8);
+}
+
+int hq_cos_topk(const void* A16, const double* inv_a, int Q, const void* B16, const double* inv_b, int64_t N, int K,
+                int k, double threshold, int thr_mode, int64_t id_base, void* workspace, size_t workspace_bytes,
+                double* out_score, int64_t* out_id, hq_stream_t stream) {
+  bool run;
+  const int rc = cos_topk_check(Q, N, K, k, A16 && inv_a && B16 && inv_b && workspace && out_score && out_id,
+                                workspace_bytes, &run, [] {
+    const int64_t ek = opt(OPT_COS_KERNEL, 0);
+    if (ek >= 1 && ek <= 3)
+      return fail(HQ_E_UNSUPPORTED, "cos_kernel=%lld prepares the row-major layout; the fused frame top-k needs the tiled one",
+                  (long long)ek);
+    return HQ_OK;
+  });
+  if (!run) return rc;
+  const hipStream_t s = (hipStream_t)stream;
+  CosArgs a;
+  a.A = reinterpret_cast<const _Float16*>(A16);
+  a.B = reinterpret_cast<const _Float16*>(B16);
+  a.ia = inv_a;
+  a.ib = inv_b;
+  a.Q = Q;
+  a.N = N;
+  a.Kp = hq_cos_padded_k(K);
+  a.ntiles = hq_cos_padded_rows(N) / kCosT;
+  a.out = nullptr;
+  a.outf = nullptr;
+  // the default kernel's K loop, top-k epilogue
+  return cos_topk_run(Q, N, k, threshold, thr_mode, id_base, workspace, out_score, out_id, s, a,
+                      [&] { return launch_t<3, 1, 1, 4>(a, s); });
 }
 
 }  // extern "C"
@@ -1104,6 +1143,7 @@ typedef int i4v __attribute__((ext_vector_type(4)));
 
 constexpr int kCosqK = 64;        // K per step
 constexpr int kCosqMaxK = 65536;  // |P| <= 2^30, K T and S_q S_c below 2^48
+constexpr int kCosqfQ = 64;       // queries per workgroup of k_cosq_t<3, EP> = the row padding of hq_cosqf_* queries
 
 struct CosqArgs {
   CosArgs c;         // Q, N, qtiles, ntiles, out, tk_*: what the shared epilogue pieces read (the rest unused)
@@ -1121,6 +1161,18 @@ __device__ __forceinline__ double cosq_score(int P, double Kd, double Aq, double
                                              double Bc, double Sc, double okc) {
   const double t = Kd * (double)P - Sq * Sc;
   const double cs = Aq * Ac + (Bq * Bc) * t;
+  return (okq != 0.0 && okc != 0.0) ? (cs + 1.0) / 2.0 : 0.0;
+}
+
+// The one pair expression of every hq_cosqf_* epilogue (D, Sv, A_q, B_q: the banner of the file's last section, three
+// query planes P0 .. P2 against one frame).  The integer part wraps nowhere that matters: K D and
+// Sv S_c reach 2^62 each, their difference is at most 2^62 in magnitude (Cauchy-Schwarz on the two centred rows),
+// and unsigned arithmetic gives that difference whatever the intermediate carries do.
+__device__ __forceinline__ double cosqf_score(int P0, int P1, int P2, int64_t K, double Aq, double Bq, int64_t Sv,
+                                              double okq, double Ac, double Bc, int64_t Sc, double okc) {
+  const int64_t D = 65536 * (int64_t)P2 + 256 * (int64_t)P1 + (int64_t)P0 + 32896 * Sc;
+  const int64_t t = (int64_t)((uint64_t)K * (uint64_t)D - (uint64_t)Sv * (uint64_t)Sc);
+  const double cs = Aq * Ac + (Bq * Bc) * (double)t;
   return (okq != 0.0 && okc != 0.0) ? (cs + 1.0) / 2.0 : 0.0;
 }
 
@@ -1205,18 +1257,24 @@ __global__ __launch_bounds__(1024) void k_cosq_prepare(const uint8_t* __restrict
   }
 }
 
-// The GEMM: k_cos_t<3, 1, 1>'s structure (128 queries x 384 frames per 8-wave workgroup, wave w = all 128
-// queries x frames 48 w .. + 47, frame fragments straight from global memory one K step ahead, query fragments
-// through two LDS stages, ping-pong: the two waves of a SIMD one barrier phase apart) with one operand plane,
-// K steps of 64 and v_mfma_i32_16x16x64_i8 into int32 accumulators.  Per K step and wave: 8 ds_read_b128,
-// 1 ds_write_b128, 1 + 3 global loads of 1 KiB, 24 MFMAs.  EP 0: float64 score stores; EP 4: the staged top-k
-// epilogue of hq_cos_topk (cos_topk_row on the same slab layout, running-threshold hint included).
-template <int EP>
+// The GEMM of hq_cosq_* (NP = 1 query plane) and hq_cosqf_* (NP = 3): k_cos_t<3, 1, 1>'s structure (384 frames per
+// 8-wave workgroup, wave w = every query x frames 48 w .. + 47, frame fragments straight from global memory one K
+// step ahead, query fragments through two LDS stages, ping-pong: the two waves of a SIMD one barrier phase apart,
+// XCD-aware block order) with K steps of 64 and v_mfma_i32_16x16x64_i8 into int32 accumulators.  A workgroup takes
+// QT query tiles of 16 x NP planes = NF fragments of 1 KiB per step and stage; fragment f = (query tile f / NP,
+// plane f % NP), wave w stages f = w and, where NF > 8, waves 0 .. NF - 9 also f = w + 8.
+//   NP 1: 128 queries, 8 fragments, 8 x 3 accumulators of 4 = 96 VGPRs; per K step and wave 8 ds_read_b128,
+//         1 ds_write_b128, 1 + 3 global loads of 1 KiB, 24 MFMAs.
+//   NP 3: 64 queries, 4 x 3 = 12 fragments, 4 x 3 x 3 accumulators of 4 = 144 VGPRs; per K step and wave
+//         12 ds_read_b128, 1 or 2 ds_write_b128, 1 or 2 + 3 global loads of 1 KiB, 36 MFMAs.
+// EP 0: float64 score stores; EP 4: the staged top-k epilogue of hq_cos_topk (cos_topk_row on the same slab layout,
+// running-threshold hint included).
+template <int NP, int EP>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_cosq_t(CosqArgs a, int64_t ftiles) {
-  constexpr int FT = 3, QT = 8, TN = 8 * 16 * FT;
-  // the epilogue's stage (8 wave slices of 16 x 48 f64); during the K loop its first 16 KiB hold the two query stages
+  constexpr int FT = 3, QT = NP == 1 ? 8 : 4, NF = QT * NP, TN = 8 * 16 * FT;
+  // the epilogue's stage (8 wave slices of 16 x 48 f64); during the K loop its first 2 NF KiB hold the two query stages
   __shared__ __attribute__((aligned(16))) uint8_t smem[8 * 16 * 16 * FT * 8];
-  int8_t(*sA)[QT * 1024] = reinterpret_cast<int8_t(*)[QT * 1024]>(smem);
+  int8_t(*sA)[NF * 1024] = reinterpret_cast<int8_t(*)[NF * 1024]>(smem);
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int64_t blk = blockIdx.x;
   const int64_t xcd = blk & 7, slot = blk >> 3;
@@ -1225,8 +1283,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
   if (nt >= a.c.ntiles) return;
   const int KB = a.KB;
   const int64_t qt0 = (int64_t)qt * QT;
-  // wave w stages query tile w of every step
-  const int8_t* srcA = a.A8 + (qt0 + wv) * KB * 1024 + 16 * lane;
+  const bool two = NF > 8 && __builtin_amdgcn_readfirstlane(wv) < NF - 8;
+  const int f1 = wv + 8;
+  const int8_t* srcA0 = a.A8 + ((qt0 + wv / NP) * KB * NP + wv % NP) * 1024 + 16 * lane;
+  const int8_t* srcA1 = a.A8 + ((qt0 + (two ? f1 / NP : 0)) * KB * NP + f1 % NP) * 1024 + 16 * lane;
   const int8_t* srcB[FT];
 #pragma unroll
   for (int j = 0; j < FT; ++j) {
@@ -1234,19 +1294,27 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
     if (t > ftiles - 1) t = ftiles - 1;  // the last frame tile may pass the padded rows
     srcB[j] = a.B8 + t * KB * 1024 + 16 * lane;
   }
-  i4v ra;
+  i4v ra0, ra1 = i4v{0, 0, 0, 0};
   i4v rb0[FT], rb1[FT];  // frame fragments of steps s, s + 1
-  auto loadA = [&](int kb) { ra = *reinterpret_cast<const i4v*>(srcA + (int64_t)kb * 1024); };
+  auto loadA = [&](int kb) {
+    ra0 = *reinterpret_cast<const i4v*>(srcA0 + (int64_t)kb * (NP * 1024));
+    if (two) ra1 = *reinterpret_cast<const i4v*>(srcA1 + (int64_t)kb * (NP * 1024));
+  };
   auto loadB = [&](int kb, i4v (&d)[FT]) {
 #pragma unroll
     for (int j = 0; j < FT; ++j) d[j] = *reinterpret_cast<const i4v*>(srcB[j] + (int64_t)kb * 1024);
   };
-  auto storeA = [&](int st) { *reinterpret_cast<i4v*>(&sA[st][wv * 1024 + 16 * lane]) = ra; };
-  i4v acc[QT][FT];
+  auto storeA = [&](int st) {
+    *reinterpret_cast<i4v*>(&sA[st][wv * 1024 + 16 * lane]) = ra0;
+    if (two) *reinterpret_cast<i4v*>(&sA[st][f1 * 1024 + 16 * lane]) = ra1;
+  };
+  i4v acc[QT][NP][FT];
 #pragma unroll
   for (int i = 0; i < QT; ++i)
 #pragma unroll
-    for (int j = 0; j < FT; ++j) acc[i][j] = i4v{0, 0, 0, 0};
+    for (int p = 0; p < NP; ++p)
+#pragma unroll
+      for (int j = 0; j < FT; ++j) acc[i][p][j] = i4v{0, 0, 0, 0};
 
   // one K step: b = frame fragments of step s, nb receives step s + 1 (k_cos_t's step, PP = 1, D = 1; past the
   // end the loads repeat the last step and the store fills a stage nobody reads again)
@@ -1256,17 +1324,19 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
     loadA(s + 2 < KB ? s + 2 : KB - 1);
     loadB(s + 1 < KB ? s + 1 : KB - 1, nb);
     __builtin_amdgcn_sched_barrier(0);
-    i4v af[QT];
+    i4v af[NF];
 #pragma unroll
-    for (int i = 0; i < QT; ++i) af[i] = *reinterpret_cast<const i4v*>(&sA[st][i * 1024 + 16 * lane]);
+    for (int f = 0; f < NF; ++f) af[f] = *reinterpret_cast<const i4v*>(&sA[st][f * 1024 + 16 * lane]);
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int i = 0; i < QT; ++i)
 #pragma unroll
-      for (int j = 0; j < FT; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[i], b[j], acc[i][j], 0, 0, 0);
+      for (int p = 0; p < NP; ++p)
+#pragma unroll
+        for (int j = 0; j < FT; ++j)
+          acc[i][p][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[NP * i + p], b[j], acc[i][p][j], 0, 0, 0);
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("s_barrier" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
@@ -1289,15 +1359,23 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
   if (!grp) asm volatile("s_barrier" ::: "memory");
   // epilogue: lane holds queries 16 i + 4 (lane >> 4) + r, frames 16 j + (lane & 15) of its wave's columns (the
   // C / D map does not depend on the operand type); sa / sb cover the padded rows, a frame column past them is
-  // clamped for the load and never stored
+  // clamped for the load and never stored.  NP 3 takes the integer sums S_c, Sv as int64, converted here, once
+  // per frame column and query row (at the use site the conversion would repeat for every pair).
   const int64_t q0 = qt0 * 16, n0 = nt * TN + (int64_t)wv * 16 * FT;
   const int64_t nrows = ftiles * 16;
   const double Kd = (double)a.K;
-  double4 sc[FT];
+  const int64_t Ki = a.K;
+  double Ac[FT], Bc[FT], Sd[FT], okc[FT];
+  int64_t Sc[FT];
 #pragma unroll
   for (int j = 0; j < FT; ++j) {
     const int64_t n = n0 + 16 * j + (lane & 15);
-    sc[j] = *reinterpret_cast<const double4*>(a.sb + 4 * (n < nrows ? n : nrows - 1));
+    const double4 c = *reinterpret_cast<const double4*>(a.sb + 4 * (n < nrows ? n : nrows - 1));
+    Ac[j] = c.x;
+    Bc[j] = c.y;
+    Sd[j] = c.z;
+    Sc[j] = (int64_t)c.z;
+    okc[j] = c.w;
   }
   double* stage = reinterpret_cast<double*>(smem) + wv * 16 * 16 * FT;
 #pragma unroll
@@ -1307,10 +1385,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
     for (int r = 0; r < 4; ++r) {
       const int64_t q = qb + r;
       const double4 sq = *reinterpret_cast<const double4*>(a.sa + 4 * q);
+      const int64_t Sv = (int64_t)sq.z;
 #pragma unroll
       for (int j = 0; j < FT; ++j) {
         const int64_t n = n0 + 16 * j + (lane & 15);
-        const double v = cosq_score(acc[i][j][r], Kd, sq.x, sq.y, sq.z, sq.w, sc[j].x, sc[j].y, sc[j].z, sc[j].w);
+        double v;
+        if constexpr (NP == 1)
+          v = cosq_score(acc[i][0][j][r], Kd, sq.x, sq.y, sq.z, sq.w, Ac[j], Bc[j], Sd[j], okc[j]);
+        else
+          v = cosqf_score(acc[i][0][j][r], acc[i][1][j][r], acc[i][2][j][r], Ki, sq.x, sq.y, Sv, sq.w, Ac[j], Bc[j],
+                          Sc[j], okc[j]);
         if constexpr (EP == 4) {  // top-k: every value is staged, rows and columns are masked in cos_topk_row
           stage[(4 * (lane >> 4) + r) * 16 * FT + 16 * j + (lane & 15)] = v;
         } else if (q < a.c.Q && n < a.c.N) {
@@ -1333,15 +1417,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
   }
 }
 
-template <int EP>
+// Query rows are padded to the workgroup's QT tiles: 128 for one plane, kCosqfQ for three.
+template <int NP, int EP>
 static int launch_cosq(CosqArgs a, hipStream_t s) {
   const int64_t np_rows = hq_cosq_padded_rows(a.c.N);
-  a.c.qtiles = (int)(hq_cosq_padded_rows(a.c.Q) / 128);
+  a.c.qtiles = (int)(NP == 1 ? hq_cosq_padded_rows(a.c.Q) / 128 : hq_cosqf_padded_rows(a.c.Q) / kCosqfQ);
   a.c.ntiles = (np_rows + 383) / 384;
   const int64_t nt8 = ((a.c.ntiles + 7) / 8) * 8;
   const int64_t blocks = nt8 * a.c.qtiles;
   if (blocks > 0x7FFFFFFF) return fail(HQ_E_UNSUPPORTED, "too many tiles");
-  hipLaunchKernelGGL(k_cosq_t<EP>, dim3((unsigned)blocks), dim3(512), 0, s, a, np_rows / 16);
+  hipLaunchKernelGGL((k_cosq_t<NP, EP>), dim3((unsigned)blocks), dim3(512), 0, s, a, np_rows / 16);
   HQ_CHECK_LAUNCH();
   return HQ_OK;
 }
@@ -1391,60 +1476,26 @@ int hq_cosq_scores(const void* A8, const double* stats_a, int Q, const void* B8,
   if (!A8 || !stats_a || !B8 || !stats_b || !out) return fail(HQ_E_INVALID, "null buffer");
   CosqArgs a = cosq_args(A8, stats_a, Q, B8, stats_b, N, K);
   a.c.out = out;
-  return launch_cosq<0>(a, (hipStream_t)stream);
+  return launch_cosq<1, 0>(a, (hipStream_t)stream);
 }
 
-// The workspace layout and the merge stage are hq_cos_topk's: [Q] hint keys, the stage-1 slab [Q, P, k] and
-// two merge buffers (P = frame tiles of 384).
+// The workspace layout, the shared checks and the merge stage are hq_cos_topk's (cos_topk_check, cos_topk_run).
 size_t hq_cosq_topk_workspace_size(int Q, int64_t N, int k) { return hq_cos_topk_workspace_size(Q, N, k); }
 
 int hq_cosq_topk(const void* A8, const double* stats_a, int Q, const void* B8, const double* stats_b, int64_t N, int K,
                  int k, double threshold, int thr_mode, int64_t id_base, void* workspace, size_t workspace_bytes,
                  double* out_score, int64_t* out_id, hq_stream_t stream) {
-  if (Q < 0 || N < 0 || K <= 0 || k < 1) return fail(HQ_E_INVALID, "bad shape Q=%d N=%lld K=%d k=%d", Q, (long long)N, K, k);
-  if (Q == 0 || N == 0) return HQ_OK;
-  if (k > 64) return fail(HQ_E_UNSUPPORTED, "k=%d: the fused frame top-k keeps lists of at most 64", k);
-  if (K > kCosqMaxK) return fail(HQ_E_UNSUPPORTED, "K=%d: the int32 accumulator holds K <= %d", K, kCosqMaxK);
-  if (!A8 || !stats_a || !B8 || !stats_b || !workspace || !out_score || !out_id) return fail(HQ_E_INVALID, "null buffer");
-  if (workspace_bytes < hq_cosq_topk_workspace_size(Q, N, k)) return fail(HQ_E_INVALID, "workspace too small");
+  bool run;
+  const int rc = cos_topk_check(Q, N, K, k, A8 && stats_a && B8 && stats_b && workspace && out_score && out_id,
+                                workspace_bytes, &run, [&] {
+    if (K > kCosqMaxK) return fail(HQ_E_UNSUPPORTED, "K=%d: the int32 accumulator holds K <= %d", K, kCosqMaxK);
+    return HQ_OK;
+  });
+  if (!run) return rc;
   const hipStream_t s = (hipStream_t)stream;
-  const int64_t P = cos_topk_tiles(N);
-  uint8_t* w = reinterpret_cast<uint8_t*>(workspace);
-  auto take = [&](size_t bytes) { uint8_t* p = w; w += cos_topk_al(bytes); return p; };
-  uint64_t* hint = reinterpret_cast<uint64_t*>(take((size_t)Q * 8));
-  double* bs[3];
-  int64_t* bi[3];
-  int64_t cap = P;  // lists per query a buffer holds: P, ceil(P / 64), ceil(P / 4096)
-  for (int i = 0; i < 3; ++i) {
-    bs[i] = reinterpret_cast<double*>(take((size_t)Q * cap * k * 8));
-    bi[i] = reinterpret_cast<int64_t*>(take((size_t)Q * cap * k * 8));
-    cap = (cap + 63) / 64;
-  }
   CosqArgs a = cosq_args(A8, stats_a, Q, B8, stats_b, N, K);
-  a.c.tk_s = bs[0];
-  a.c.tk_id = bi[0];
-  a.c.tk_hint = opt(OPT_COS_TOPK_HINT, 1) ? hint : nullptr;
-  a.c.tk_thr = threshold;
-  a.c.tk_mode = thr_mode;
-  a.c.tk_k = k;
-  if (a.c.tk_hint) HQ_CHECK_HIP(hipMemsetAsync(hint, 0, (size_t)Q * 8, s));
-  const int rc = launch_cosq<4>(a, s);
-  if (rc != HQ_OK) return rc;
-  int64_t Pc = P;
-  int cur = 0;
-  for (;;) {  // merge 64 lists at a time until one is left, as hq_cos_topk does
-    const int64_t P2 = (Pc + 63) / 64;
-    const bool last = P2 == 1;
-    const int nxt = cur == 1 ? 2 : 1;
-    const int64_t g = (int64_t)Q * P2 < 65536 ? (int64_t)Q * P2 : 65536;
-    hipLaunchKernelGGL(k_cos_topk_merge, dim3((unsigned)g), dim3(64), 0, s, Q, Pc, P2, k, last ? id_base : (int64_t)0,
-                       (const double*)bs[cur], (const int64_t*)bi[cur], last ? out_score : bs[nxt], last ? out_id : bi[nxt]);
-    HQ_CHECK_LAUNCH();
-    if (last) break;
-    Pc = P2;
-    cur = nxt;
-  }
-  return HQ_OK;
+  return cos_topk_run(Q, N, k, threshold, thr_mode, id_base, workspace, out_score, out_id, s, a.c,
+                      [&] { return launch_cosq<1, 4>(a, s); });
 }
 
 }  // extern "C"
@@ -1465,19 +1516,6 @@ int hq_cosq_topk(const void* A8, const double* stats_a, int Q, const void* B8, c
 // corpus's fragment layout (lane 16 g + j = row 16 t + j, bytes 64 kb + 16 g .. + 15): a step's query operands are
 // one contiguous 3 KiB.  stats [padded rows, 4] = (A_q, B_q, Sv, ok); Sv is an integer below 2^39, exact as f64.
 namespace hq {
-
-constexpr int kCosqfQ = 64;  // queries per workgroup of k_cosqf_t = the row padding of the query operands
-
-// The one pair expression of every hq_cosqf_* epilogue.  The integer part wraps nowhere that matters: K D and
-// Sv S_c reach 2^62 each, their difference is at most 2^62 in magnitude (Cauchy-Schwarz on the two centred rows),
-// and unsigned arithmetic gives that difference whatever the intermediate carries do.
-__device__ __forceinline__ double cosqf_score(int P0, int P1, int P2, int64_t K, double Aq, double Bq, int64_t Sv,
-                                              double okq, double Ac, double Bc, int64_t Sc, double okc) {
-  const int64_t D = 65536 * (int64_t)P2 + 256 * (int64_t)P1 + (int64_t)P0 + 32896 * Sc;
-  const int64_t t = (int64_t)((uint64_t)K * (uint64_t)D - (uint64_t)Sv * (uint64_t)Sc);
-  const double cs = Aq * Ac + (Bq * Bc) * (double)t;
-  return (okq != 0.0 && okc != 0.0) ? (cs + 1.0) / 2.0 : 0.0;
-}
 
 // One 16-wave workgroup per 16-row query tile, two passes over the floats (the second one hits the cache).
 // Pass 1: the largest |q| bit pattern of every row (a NaN or inf is above every finite pattern, so one integer
@@ -1597,166 +1635,6 @@ __global__ __launch_bounds__(1024) void k_cosqf_prepare(const float* __restrict_
   }
 }
 
-// The GEMM: k_cosq_t's structure (384 frames per 8-wave workgroup, wave w = frames 48 w .. + 47, frame fragments
-// straight from global memory one K step ahead, query fragments through two LDS stages, ping-pong between the two
-// waves of a SIMD, XCD-aware block order) with three query planes: 64 queries per workgroup, 4 query tiles x 3
-// planes = 12 fragments (12 KiB) per step and stage, 4 x 3 x 3 int32 accumulators of 4 = 144 VGPRs.  Waves 0-3
-// stage two fragments of a step (w and w + 8), waves 4-7 one.  Per K step and wave: 12 ds_read_b128, 1 or 2
-// ds_write_b128, 1 or 2 + 3 global loads of 1 KiB, 36 MFMAs.  EP 0: float64 score stores; EP 4: the staged top-k
-// epilogue of hq_cos_topk (cos_topk_row on the same slab layout, running-threshold hint included).
-template <int EP>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_cosqf_t(CosqArgs a, int64_t ftiles) {
-  constexpr int FT = 3, QT = kCosqfQ / 16, NP = 3, NF = QT * NP, TN = 8 * 16 * FT;
-  // the epilogue's stage (8 wave slices of 16 x 48 f64); during the K loop its first 24 KiB hold the two query stages
-  __shared__ __attribute__((aligned(16))) uint8_t smem[8 * 16 * 16 * FT * 8];
-  int8_t(*sA)[NF * 1024] = reinterpret_cast<int8_t(*)[NF * 1024]>(smem);
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int64_t blk = blockIdx.x;
-  const int64_t xcd = blk & 7, slot = blk >> 3;
-  const int qt = (int)(slot % a.c.qtiles);
-  const int64_t nt = xcd + 8 * (slot / a.c.qtiles);
-  if (nt >= a.c.ntiles) return;
-  const int KB = a.KB;
-  const int64_t qt0 = (int64_t)qt * QT;
-  // fragment f of a step = (query tile f / 3, plane f % 3); wave w stages f = w, waves 0-3 also f = w + 8
-  const bool two = __builtin_amdgcn_readfirstlane(wv) < NF - 8;
-  const int f1 = wv + 8;
-  const int8_t* srcA0 = a.A8 + ((qt0 + wv / NP) * KB * NP + wv % NP) * 1024 + 16 * lane;
-  const int8_t* srcA1 = a.A8 + ((qt0 + (two ? f1 / NP : 0)) * KB * NP + f1 % NP) * 1024 + 16 * lane;
-  const int8_t* srcB[FT];
-#pragma unroll
-  for (int j = 0; j < FT; ++j) {
-    int64_t t = nt * (TN / 16) + wv * FT + j;
-    if (t > ftiles - 1) t = ftiles - 1;  // the last frame tile may pass the padded rows
-    srcB[j] = a.B8 + t * KB * 1024 + 16 * lane;
-  }
-  i4v ra0, ra1 = i4v{0, 0, 0, 0};
-  i4v rb0[FT], rb1[FT];  // frame fragments of steps s, s + 1
-  auto loadA = [&](int kb) {
-    ra0 = *reinterpret_cast<const i4v*>(srcA0 + (int64_t)kb * (NP * 1024));
-    if (two) ra1 = *reinterpret_cast<const i4v*>(srcA1 + (int64_t)kb * (NP * 1024));
-  };
-  auto loadB = [&](int kb, i4v (&d)[FT]) {
-#pragma unroll
-    for (int j = 0; j < FT; ++j) d[j] = *reinterpret_cast<const i4v*>(srcB[j] + (int64_t)kb * 1024);
-  };
-  auto storeA = [&](int st) {
-    *reinterpret_cast<i4v*>(&sA[st][wv * 1024 + 16 * lane]) = ra0;
-    if (two) *reinterpret_cast<i4v*>(&sA[st][f1 * 1024 + 16 * lane]) = ra1;
-  };
-  i4v acc[QT][NP][FT];
-#pragma unroll
-  for (int i = 0; i < QT; ++i)
-#pragma unroll
-    for (int p = 0; p < NP; ++p)
-#pragma unroll
-      for (int j = 0; j < FT; ++j) acc[i][p][j] = i4v{0, 0, 0, 0};
-
-  // one K step, as k_cosq_t's
-  auto step = [&](int s, const i4v (&b)[FT], i4v (&nb)[FT]) {
-    const int st = s & 1;
-    storeA(st ^ 1);
-    loadA(s + 2 < KB ? s + 2 : KB - 1);
-    loadB(s + 1 < KB ? s + 1 : KB - 1, nb);
-    __builtin_amdgcn_sched_barrier(0);
-    i4v af[NF];
-#pragma unroll
-    for (int f = 0; f < NF; ++f) af[f] = *reinterpret_cast<const i4v*>(&sA[st][f * 1024 + 16 * lane]);
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int i = 0; i < QT; ++i)
-#pragma unroll
-      for (int p = 0; p < NP; ++p)
-#pragma unroll
-        for (int j = 0; j < FT; ++j)
-          acc[i][p][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[NP * i + p], b[j], acc[i][p][j], 0, 0, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_barrier" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-  };
-
-  loadA(0);
-  loadB(0, rb0);
-  storeA(0);
-  loadA(KB > 1 ? 1 : 0);
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  // ping-pong as in k_cos_t: group 1 (waves 4-7) one barrier phase behind, group 0 one extra barrier at the end
-  const int grp = __builtin_amdgcn_readfirstlane(wv >> 2);
-  if (grp) asm volatile("s_barrier" ::: "memory");
-  int s = 0;
-  for (; s + 2 <= KB; s += 2) {
-    step(s, rb0, rb1);
-    step(s + 1, rb1, rb0);
-  }
-  if (s < KB) step(s, rb0, rb1);
-  if (!grp) asm volatile("s_barrier" ::: "memory");
-  // epilogue: lane holds queries 16 i + 4 (lane >> 4) + r, frames 16 j + (lane & 15) of its wave's columns; sa
-  // covers the padded query rows, a frame column past the padded frame rows is clamped for the load, never stored
-  const int64_t q0 = qt0 * 16, n0 = nt * TN + (int64_t)wv * 16 * FT;
-  const int64_t nrows = ftiles * 16;
-  const int64_t Ki = a.K;
-  double Ac[FT], Bc[FT], okc[FT];
-  int64_t Sc[FT];
-#pragma unroll
-  for (int j = 0; j < FT; ++j) {
-    const int64_t n = n0 + 16 * j + (lane & 15);
-    const double4 c = *reinterpret_cast<const double4*>(a.sb + 4 * (n < nrows ? n : nrows - 1));
-    Ac[j] = c.x;
-    Bc[j] = c.y;
-    Sc[j] = (int64_t)c.z;
-    okc[j] = c.w;
-  }
-  double* stage = reinterpret_cast<double*>(smem) + wv * 16 * 16 * FT;
-#pragma unroll
-  for (int i = 0; i < QT; ++i) {
-    const int64_t qb = q0 + 16 * i + 4 * (lane >> 4);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int64_t q = qb + r;
-      const double4 sq = *reinterpret_cast<const double4*>(a.sa + 4 * q);
-      const int64_t Sv = (int64_t)sq.z;
-#pragma unroll
-      for (int j = 0; j < FT; ++j) {
-        const int64_t n = n0 + 16 * j + (lane & 15);
-        const double v = cosqf_score(acc[i][0][j][r], acc[i][1][j][r], acc[i][2][j][r], Ki, sq.x, sq.y, Sv, sq.w,
-                                     Ac[j], Bc[j], Sc[j], okc[j]);
-        if constexpr (EP == 4) {  // top-k: every value is staged, rows and columns are masked in cos_topk_row
-          stage[(4 * (lane >> 4) + r) * 16 * FT + 16 * j + (lane & 15)] = v;
-        } else if (q < a.c.Q && n < a.c.N) {
-          __builtin_nontemporal_store(v, a.c.out + q * a.c.N + n);  // write-once scores
-        }
-      }
-    }
-    if constexpr (EP == 4) {
-      // as k_cos_t's EP 4: wave w selects for queries 2 w and 2 w + 1 of the row block; every wave of the
-      // workgroup reaches both barriers of every row block
-      __syncthreads();
-#pragma unroll 1
-      for (int h = 0; h < 2; ++h) {
-        const int row = 2 * wv + h;
-        const int64_t q = q0 + 16 * i + row;
-        if (q < a.c.Q) cos_topk_row<TN>(reinterpret_cast<const double*>(smem), row, q, nt, a.c);
-      }
-      __syncthreads();  // the next row block overwrites the stage
-    }
-  }
-}
-
-template <int EP>
-static int launch_cosqf(CosqArgs a, hipStream_t s) {
-  const int64_t np_rows = hq_cosq_padded_rows(a.c.N);
-  a.c.qtiles = (int)(hq_cosqf_padded_rows(a.c.Q) / kCosqfQ);
-  a.c.ntiles = (np_rows + 383) / 384;
-  const int64_t nt8 = ((a.c.ntiles + 7) / 8) * 8;
-  const int64_t blocks = nt8 * a.c.qtiles;
-  if (blocks > 0x7FFFFFFF) return fail(HQ_E_UNSUPPORTED, "too many tiles");
-  hipLaunchKernelGGL(k_cosqf_t<EP>, dim3((unsigned)blocks), dim3(512), 0, s, a, np_rows / 16);
-  HQ_CHECK_LAUNCH();
-  return HQ_OK;
-}
-
 }  // namespace hq
 
 extern "C" {
@@ -1786,7 +1664,7 @@ int hq_cosqf_scores(const void* Q8, const double* stats_q, int Q, const void* B8
   if (!Q8 || !stats_q || !B8 || !stats_b || !out) return fail(HQ_E_INVALID, "null buffer");
   CosqArgs a = cosq_args(Q8, stats_q, Q, B8, stats_b, N, K);
   a.c.out = out;
-  return launch_cosqf<0>(a, (hipStream_t)stream);
+  return launch_cosq<3, 0>(a, (hipStream_t)stream);
 }
 
 // Workspace layout and merge stage: hq_cos_topk's, as hq_cosq_topk.
@@ -1795,50 +1673,17 @@ size_t hq_cosqf_topk_workspace_size(int Q, int64_t N, int k) { return hq_cos_top
 int hq_cosqf_topk(const void* Q8, const double* stats_q, int Q, const void* B8, const double* stats_b, int64_t N, int K,
                   int k, double threshold, int thr_mode, int64_t id_base, void* workspace, size_t workspace_bytes,
                   double* out_score, int64_t* out_id, hq_stream_t stream) {
-  if (Q < 0 || N < 0 || K <= 0 || k < 1) return fail(HQ_E_INVALID, "bad shape Q=%d N=%lld K=%d k=%d", Q, (long long)N, K, k);
-  if (Q == 0 || N == 0) return HQ_OK;
-  if (k > 64) return fail(HQ_E_UNSUPPORTED, "k=%d: the fused frame top-k keeps lists of at most 64", k);
-  if (K > kCosqMaxK) return fail(HQ_E_UNSUPPORTED, "K=%d: the int32 accumulators hold K <= %d", K, kCosqMaxK);
-  if (!Q8 || !stats_q || !B8 || !stats_b || !workspace || !out_score || !out_id) return fail(HQ_E_INVALID, "null buffer");
-  if (workspace_bytes < hq_cosqf_topk_workspace_size(Q, N, k)) return fail(HQ_E_INVALID, "workspace too small");
+  bool run;
+  const int rc = cos_topk_check(Q, N, K, k, Q8 && stats_q && B8 && stats_b && workspace && out_score && out_id,
+                                workspace_bytes, &run, [&] {
+    if (K > kCosqMaxK) return fail(HQ_E_UNSUPPORTED, "K=%d: the int32 accumulators hold K <= %d", K, kCosqMaxK);
+    return HQ_OK;
+  });
+  if (!run) return rc;
   const hipStream_t s = (hipStream_t)stream;
-  const int64_t P = cos_topk_tiles(N);
-  uint8_t* w = reinterpret_cast<uint8_t*>(workspace);
-  auto take = [&](size_t bytes) { uint8_t* p = w; w += cos_topk_al(bytes); return p; };
-  uint64_t* hint = reinterpret_cast<uint64_t*>(take((size_t)Q * 8));
-  double* bs[3];
-  int64_t* bi[3];
-  int64_t cap = P;  // lists per query a buffer holds: P, ceil(P / 64), ceil(P / 4096)
-  for (int i = 0; i < 3; ++i) {
-    bs[i] = reinterpret_cast<double*>(take((size_t)Q * cap * k * 8));
-    bi[i] = reinterpret_cast<int64_t*>(take((size_t)Q * cap * k * 8));
-    cap = (cap + 63) / 64;
-  }
   CosqArgs a = cosq_args(Q8, stats_q, Q, B8, stats_b, N, K);
-  a.c.tk_s = bs[0];
-  a.c.tk_id = bi[0];
-  a.c.tk_hint = opt(OPT_COS_TOPK_HINT, 1) ? hint : nullptr;
-  a.c.tk_thr = threshold;
-  a.c.tk_mode = thr_mode;
-  a.c.tk_k = k;
-  if (a.c.tk_hint) HQ_CHECK_HIP(hipMemsetAsync(hint, 0, (size_t)Q * 8, s));
-  const int rc = launch_cosqf<4>(a, s);
-  if (rc != HQ_OK) return rc;
-  int64_t Pc = P;
-  int cur = 0;
-  for (;;) {  // merge 64 lists at a time until one is left, as hq_cos_topk does
-    const int64_t P2 = (Pc + 63) / 64;
-    const bool last = P2 == 1;
-    const int nxt = cur == 1 ? 2 : 1;
-    const int64_t g = (int64_t)Q * P2 < 65536 ? (int64_t)Q * P2 : 65536;
-    hipLaunchKernelGGL(k_cos_topk_merge, dim3((unsigned)g), dim3(64), 0, s, Q, Pc, P2, k, last ? id_base : (int64_t)0,
-                       (const double*)bs[cur], (const int64_t*)bi[cur], last ? out_score : bs[nxt], last ? out_id : bi[nxt]);
-    HQ_CHECK_LAUNCH();
-    if (last) break;
-    Pc = P2;
-    cur = nxt;
-  }
-  return HQ_OK;
+  return cos_topk_run(Q, N, k, threshold, thr_mode, id_base, workspace, out_score, out_id, s, a.c,
+                      [&] { return launch_cosq<3, 4>(a, s); });
 }
 
 }  // extern "C"

@@ -1021,26 +1021,26 @@ def cosine_scores_mfma(q: CosRows, c: CosRows, exc=None, f32: bool = False):
     return out
 
 
-def _cos_query_block(q: CosRows, q0: int, q1: int) -> CosRows:
-    """Prepared queries [q0, q1), q0 a multiple of 16: query tile t starts at X16[16 t] (1 KiB fragments,
-    tile-major), so a block is a pointer offset into the prepared rows."""
-    return q if (q0 == 0 and q1 == q.N) else CosRows(q.X16[q0:], q.inv[q0:], q1 - q0, q.K)
+def _query_block(q, q0: int, q1: int, operands):
+    """Prepared queries [q0, q1) of CosRows / CosQRows / CosQFRows, q0 a multiple of 16: query tile t starts at
+    row 16 t of the operand (1 KiB fragments, tile-major), so a block is a pointer offset into the prepared rows."""
+    if q0 == 0 and q1 == q.N:
+        return q
+    x, v = operands(q)
+    return type(q)(x[q0:], v[q0:], q1 - q0, q.K)
 
 
-def cosine_topk(q: CosRows, c: CosRows, k: int, threshold: float = 0.0, thr_mode: int = 0, id_base: int = 0,
-                workspace_limit: int = 256 << 20, exc=None):
-    """The k nearest prepared frames of every prepared query -> (scores [Q, k] f64, ids [Q, k] i64), equal to
-    select_topk(cosine_scores_mfma(q, c), k, threshold, thr_mode, id_base) in ids, order and score bits,
-    without the [Q, N] matrix (hq_cos_topk: the selection runs in the GEMM's epilogue).  The workspace is
-    about 16 Q k N / 384 bytes; above workspace_limit the queries run in blocks of a multiple of 128.
-    k > 64 or k > N: the dense scores and select_topk, in query blocks under the same limit."""
+def _frame_topk(q, c, k, threshold, thr_mode, id_base, workspace_limit, exc, *, dense, size, fused, operands):
+    """The body of cosine_topk, cosq_topk and cosqf_topk.  dense(q, c, exc): the route's [Q, N] scores; size /
+    fused: its hq_*_topk_workspace_size / hq_*_topk; operands(rows): (operand fragments, per-row vector)."""
     t = torch()
     if q.K != c.K:
         raise ValueError(f"query length {q.K} != frame length {c.K}")
     k, Q, N = int(k), q.N, c.N
     if k < 1:
         raise ValueError(f"k = {k}")
-    dev = q.X16.device
+    cx, cv = operands(c)
+    dev = operands(q)[0].device
     os_ = t.full((Q, k), float("-inf"), dtype=t.float64, device=dev)
     oi = t.full((Q, k), -1, dtype=t.int64, device=dev)
     if Q == 0 or N == 0:
@@ -1050,11 +1050,10 @@ def cosine_topk(q: CosRows, c: CosRows, k: int, threshold: float = 0.0, thr_mode
         per = max(128, limit // (8 * N) // 128 * 128)
         for q0 in range(0, Q, per):
             q1 = min(Q, q0 + per)
-            s, i, _, _ = select_topk(cosine_scores_mfma(_cos_query_block(q, q0, q1), c, exc), k, threshold, thr_mode,
-                                     id_base, exc)
+            s, i, _, _ = select_topk(dense(_query_block(q, q0, q1, operands), c, exc), k, threshold, thr_mode, id_base,
+                                     exc)
             os_[q0:q1], oi[q0:q1] = s, i
         return os_, oi
-    size = _L().hq_cos_topk_workspace_size
     per = Q
     if int(size(Q, N, k)) > limit:
         per = max(128, limit // max(int(size(128, N, k)), 1) * 128)
@@ -1062,12 +1061,25 @@ def cosine_topk(q: CosRows, c: CosRows, k: int, threshold: float = 0.0, thr_mode
             per -= 128
     for q0 in range(0, Q, per):
         q1 = min(Q, q0 + per)
-        b = _cos_query_block(q, q0, q1)
+        b = _query_block(q, q0, q1, operands)
+        bx, bv = operands(b)
         wb = int(size(b.N, N, k))
         ws = _workspace(wb, dev)
-        _chk(_L().hq_cos_topk(ptr(b.X16), ptr(b.inv), b.N, ptr(c.X16), ptr(c.inv), N, q.K, k, float(threshold),
-                              int(thr_mode), int(id_base), ptr(ws), wb, ptr(os_[q0:q1]), ptr(oi[q0:q1]), stream()), exc)
+        _chk(fused(ptr(bx), ptr(bv), b.N, ptr(cx), ptr(cv), N, q.K, k, float(threshold), int(thr_mode), int(id_base),
+                   ptr(ws), wb, ptr(os_[q0:q1]), ptr(oi[q0:q1]), stream()), exc)
     return os_, oi
+
+
+def cosine_topk(q: CosRows, c: CosRows, k: int, threshold: float = 0.0, thr_mode: int = 0, id_base: int = 0,
+                workspace_limit: int = 256 << 20, exc=None):
+    """The k nearest prepared frames of every prepared query -> (scores [Q, k] f64, ids [Q, k] i64), equal to
+    select_topk(cosine_scores_mfma(q, c), k, threshold, thr_mode, id_base) in ids, order and score bits,
+    without the [Q, N] matrix (hq_cos_topk: the selection runs in the GEMM's epilogue).  The workspace is
+    about 16 Q k N / 384 bytes; above workspace_limit the queries run in blocks of a multiple of 128.
+    k > 64 or k > N: the dense scores and select_topk, in query blocks under the same limit."""
+    return _frame_topk(q, c, k, threshold, thr_mode, id_base, workspace_limit, exc, dense=cosine_scores_mfma,
+                       size=_L().hq_cos_topk_workspace_size, fused=_L().hq_cos_topk,
+                       operands=lambda r: (r.X16, r.inv))
 
 
 MFMA_COS_MIN_WORK = 1 << 22
@@ -1104,27 +1116,31 @@ class CosQRows:
         return self.X8.numel() * self.X8.element_size() + self.stats.numel() * self.stats.element_size()
 
 
+def _frame_rows(x, rows: Optional[int], what: str, n: str):
+    """x [N, r, c] (or rows [N, K]) -> (x2 [N, row length] read in place, N, K): K = rows * c values out of every
+    r * c, every row by default.  what / n: the argument's name and its row-count letter in the messages."""
+    if x.dim() < 2:
+        raise ValueError(f"{what} must be [{n}, ...]")
+    N = int(x.shape[0])
+    if x.dim() == 2:
+        if rows is not None:
+            raise ValueError(f"rows= needs frames [{n}, r, c]")
+        x2 = x if x.stride(-1) == 1 else x.contiguous()
+        return x2, N, int(x2.shape[1])
+    r, c = int(x.shape[1]), int(np.prod(x.shape[2:]))
+    rows = r if rows is None else int(rows)
+    if not 1 <= rows <= r:
+        raise ValueError(f"rows = {rows} of {r}")
+    return _contig(x).view(N, r * c), N, rows * c
+
+
 def cosq_prepare(frames, minmax, rows: Optional[int] = None, exc=None) -> CosQRows:
     """u8 frames [N, r, c] (or rows [N, K]) with minmax f32 [N, 2] -> CosQRows of the first `rows` rows of every
     frame (all of them by default).  The frames are read in place: K = rows * c bytes out of every r * c."""
     t = torch()
     if frames.dtype != t.uint8:
         raise TypeError("cosq_prepare expects uint8 frames (quantise float32 rows with map_index_quantize / quantize_u8)")
-    if frames.dim() < 2:
-        raise ValueError("frames must be [N, ...]")
-    N = int(frames.shape[0])
-    if frames.dim() == 2:
-        if rows is not None:
-            raise ValueError("rows= needs frames [N, r, c]")
-        x2 = frames if frames.stride(-1) == 1 else frames.contiguous()
-        K = int(x2.shape[1])
-    else:
-        r, c = int(frames.shape[1]), int(np.prod(frames.shape[2:]))
-        rows = r if rows is None else int(rows)
-        if not 1 <= rows <= r:
-            raise ValueError(f"rows = {rows} of {r}")
-        x2 = _contig(frames).view(N, r * c)
-        K = rows * c
+    x2, N, K = _frame_rows(frames, rows, "frames", "N")
     mm = _contig(minmax.reshape(-1, 2).to(t.float32))
     if int(mm.shape[0]) != N:
         raise ValueError(f"{int(mm.shape[0])} (min, max) pairs for {N} frames")
@@ -1149,50 +1165,14 @@ def cosq_scores(q: CosQRows, c: CosQRows, exc=None):
     return out
 
 
-def _cosq_query_block(q: CosQRows, q0: int, q1: int) -> CosQRows:
-    """Prepared queries [q0, q1), q0 a multiple of 16 (fragments are tile-major: a block is a pointer offset)."""
-    return q if (q0 == 0 and q1 == q.N) else CosQRows(q.X8[q0:], q.stats[q0:], q1 - q0, q.K)
-
-
 def cosq_topk(q: CosQRows, c: CosQRows, k: int, threshold: float = 0.0, thr_mode: int = 0, id_base: int = 0,
               workspace_limit: int = 256 << 20, exc=None):
     """The k nearest prepared u8 frames of every prepared u8 query -> (scores [Q, k] f64, ids [Q, k] i64), equal to
     select_topk(cosq_scores(q, c), k, threshold, thr_mode, id_base) in ids, order and score bits (hq_cosq_topk).
     Workspace, query blocks under workspace_limit and the dense route for k > 64 or k > N: as cosine_topk."""
-    t = torch()
-    if q.K != c.K:
-        raise ValueError(f"query length {q.K} != frame length {c.K}")
-    k, Q, N = int(k), q.N, c.N
-    if k < 1:
-        raise ValueError(f"k = {k}")
-    dev = q.X8.device
-    os_ = t.full((Q, k), float("-inf"), dtype=t.float64, device=dev)
-    oi = t.full((Q, k), -1, dtype=t.int64, device=dev)
-    if Q == 0 or N == 0:
-        return os_, oi
-    limit = max(int(workspace_limit), 1)
-    if k > 64 or k > N:
-        per = max(128, limit // (8 * N) // 128 * 128)
-        for q0 in range(0, Q, per):
-            q1 = min(Q, q0 + per)
-            s, i, _, _ = select_topk(cosq_scores(_cosq_query_block(q, q0, q1), c, exc), k, threshold, thr_mode,
-                                     id_base, exc)
-            os_[q0:q1], oi[q0:q1] = s, i
-        return os_, oi
-    size = _L().hq_cosq_topk_workspace_size
-    per = Q
-    if int(size(Q, N, k)) > limit:
-        per = max(128, limit // max(int(size(128, N, k)), 1) * 128)
-        while per > 128 and int(size(per, N, k)) > limit:
-            per -= 128
-    for q0 in range(0, Q, per):
-        q1 = min(Q, q0 + per)
-        b = _cosq_query_block(q, q0, q1)
-        wb = int(size(b.N, N, k))
-        ws = _workspace(wb, dev)
-        _chk(_L().hq_cosq_topk(ptr(b.X8), ptr(b.stats), b.N, ptr(c.X8), ptr(c.stats), N, q.K, k, float(threshold),
-                               int(thr_mode), int(id_base), ptr(ws), wb, ptr(os_[q0:q1]), ptr(oi[q0:q1]), stream()), exc)
-    return os_, oi
+    return _frame_topk(q, c, k, threshold, thr_mode, id_base, workspace_limit, exc, dense=cosq_scores,
+                       size=_L().hq_cosq_topk_workspace_size, fused=_L().hq_cosq_topk,
+                       operands=lambda r: (r.X8, r.stats))
 
 
 # ------------------------------------------------ float32 queries against the u8 frame store (exact, asymmetric)
@@ -1219,21 +1199,7 @@ def cosqf_prepare(x, rows: Optional[int] = None, exc=None) -> CosQFRows:
     t = torch()
     if x.dtype != t.float32:
         raise TypeError("cosqf_prepare expects float32 queries (u8 query frames go through cosq_prepare)")
-    if x.dim() < 2:
-        raise ValueError("queries must be [Q, ...]")
-    Q = int(x.shape[0])
-    if x.dim() == 2:
-        if rows is not None:
-            raise ValueError("rows= needs frames [Q, r, c]")
-        x2 = x if x.stride(-1) == 1 else x.contiguous()
-        K = int(x2.shape[1])
-    else:
-        r, c = int(x.shape[1]), int(np.prod(x.shape[2:]))
-        rows = r if rows is None else int(rows)
-        if not 1 <= rows <= r:
-            raise ValueError(f"rows = {rows} of {r}")
-        x2 = _contig(x).view(Q, r * c)
-        K = rows * c
+    x2, Q, K = _frame_rows(x, rows, "queries", "Q")
     Kp = int(_L().hq_cosq_padded_k(K))
     Qp = int(_L().hq_cosqf_padded_rows(Q))
     Q8 = t.empty((max(Qp, 1), 3 * max(Kp, 1)), dtype=t.int8, device=x2.device)
@@ -1256,48 +1222,12 @@ def cosqf_scores(q: CosQFRows, c: CosQRows, exc=None):
     return out
 
 
-def _cosqf_query_block(q: CosQFRows, q0: int, q1: int) -> CosQFRows:
-    """Prepared queries [q0, q1), q0 a multiple of 16 (fragments are tile-major: a block is a pointer offset)."""
-    return q if (q0 == 0 and q1 == q.N) else CosQFRows(q.Q8[q0:], q.stats[q0:], q1 - q0, q.K)
-
-
 def cosqf_topk(q: CosQFRows, c: CosQRows, k: int, threshold: float = 0.0, thr_mode: int = 0, id_base: int = 0,
                workspace_limit: int = 256 << 20, exc=None):
     """The k nearest prepared u8 frames of every prepared float32 query -> (scores [Q, k] f64, ids [Q, k] i64),
     equal to select_topk(cosqf_scores(q, c), k, threshold, thr_mode, id_base) in ids, order and score bits
     (hq_cosqf_topk).  Workspace, query blocks under workspace_limit and the dense route for k > 64 or k > N: as
     cosq_topk."""
-    t = torch()
-    if q.K != c.K:
-        raise ValueError(f"query length {q.K} != frame length {c.K}")
-    k, Q, N = int(k), q.N, c.N
-    if k < 1:
-        raise ValueError(f"k = {k}")
-    dev = q.Q8.device
-    os_ = t.full((Q, k), float("-inf"), dtype=t.float64, device=dev)
-    oi = t.full((Q, k), -1, dtype=t.int64, device=dev)
-    if Q == 0 or N == 0:
-        return os_, oi
-    limit = max(int(workspace_limit), 1)
-    if k > 64 or k > N:
-        per = max(128, limit // (8 * N) // 128 * 128)
-        for q0 in range(0, Q, per):
-            q1 = min(Q, q0 + per)
-            s, i, _, _ = select_topk(cosqf_scores(_cosqf_query_block(q, q0, q1), c, exc), k, threshold, thr_mode,
-                                     id_base, exc)
-            os_[q0:q1], oi[q0:q1] = s, i
-        return os_, oi
-    size = _L().hq_cosqf_topk_workspace_size
-    per = Q
-    if int(size(Q, N, k)) > limit:
-        per = max(128, limit // max(int(size(128, N, k)), 1) * 128)
-        while per > 128 and int(size(per, N, k)) > limit:
-            per -= 128
-    for q0 in range(0, Q, per):
-        q1 = min(Q, q0 + per)
-        b = _cosqf_query_block(q, q0, q1)
-        wb = int(size(b.N, N, k))
-        ws = _workspace(wb, dev)
-        _chk(_L().hq_cosqf_topk(ptr(b.Q8), ptr(b.stats), b.N, ptr(c.X8), ptr(c.stats), N, q.K, k, float(threshold),
-                                int(thr_mode), int(id_base), ptr(ws), wb, ptr(os_[q0:q1]), ptr(oi[q0:q1]), stream()), exc)
-    return os_, oi
+    return _frame_topk(q, c, k, threshold, thr_mode, id_base, workspace_limit, exc, dense=cosqf_scores,
+                       size=_L().hq_cosqf_topk_workspace_size, fused=_L().hq_cosqf_topk,
+                       operands=lambda r: (r.Q8 if isinstance(r, CosQFRows) else r.X8, r.stats))
