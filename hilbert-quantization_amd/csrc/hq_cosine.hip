@@ -1176,6 +1176,65 @@ __device__ __forceinline__ double cosqf_score(int P0, int P1, int P2, int64_t K,
   return (okq != 0.0 && okc != 0.0) ? (cs + 1.0) / 2.0 : 0.0;
 }
 
+// Piece (kb, g) of a frame x of K bytes as k_cosq_prepare forms it: u ^ 0x80, zero past K (and for live = false).
+__device__ __forceinline__ uint4 cosq_piece(const uint8_t* __restrict__ x, int k0, int K, int fast, bool live) {
+  uint32_t w[4] = {0u, 0u, 0u, 0u};
+  if (live && k0 < K) {
+    if (fast && k0 + 16 <= K) {
+      const uint4 v = *reinterpret_cast<const uint4*>(x + k0);
+      w[0] = v.x ^ 0x80808080u;
+      w[1] = v.y ^ 0x80808080u;
+      w[2] = v.z ^ 0x80808080u;
+      w[3] = v.w ^ 0x80808080u;
+    } else {
+#pragma unroll
+      for (int u = 0; u < 16; ++u)
+        if (k0 + u < K) w[u >> 2] |= (uint32_t)(x[k0 + u] ^ 0x80u) << (8 * (u & 3));
+    }
+  }
+  return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+__device__ __forceinline__ void cosq_piece_sums(uint4 p, int& S, int& T) {
+  const uint32_t w[4] = {p.x, p.y, p.z, p.w};
+#pragma unroll
+  for (int d = 0; d < 4; ++d)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int v = (int)(int8_t)(w[d] >> (8 * b));
+      S += v;
+      T += v * v;
+    }
+}
+
+// The row statistics of the contract (include/hq_mi355x.h) from the exact sums S and T: (A, B, S, ok) at o.  mm: the
+// row's float32 (mn, mx), nullptr for a pad row, which gets (0, 0, S, 0) with S = 0.  The one copy of the expression:
+// k_cosq_prepare and the writers of the mutable store (k_cosq_append, k_cosq_replace) call it.
+__device__ __forceinline__ void cosq_row_stats(int K, int64_t Si, int64_t Ti, const float* __restrict__ mm,
+                                               double* __restrict__ o) {
+  double A = 0.0, B = 0.0, ok = 0.0;
+  if (mm) {
+    const float fmn = mm[0], fmx = mm[1];
+    if (isfinite(fmn) && isfinite(fmx)) {
+      const double mn = fmn, mx = fmx, Kd = K;
+      const double s = mx == mn ? 0.0 : (mx - mn) / 255.0;
+      const double m = mn + s * (128.0 + (double)Si / Kd);
+      const int64_t V = (int64_t)K * Ti - Si * Si;  // >= 0 (Cauchy-Schwarz), below 2^47
+      const double n2 = m * m + (s * s) * ((double)V / (Kd * Kd));  // n^2 / K
+      if (n2 > 0.0) {
+        const double inv = 1.0 / sqrt(n2);
+        A = m * inv;
+        B = (s * inv) / Kd;
+        ok = 1.0;
+      }
+    }
+  }
+  o[0] = A;
+  o[1] = B;
+  o[2] = (double)Si;
+  o[3] = ok;
+}
+
 // One 16-wave workgroup per 16-row tile, one pass over the bytes: the waves split the tile's K steps, lane
 // 16 g + j flips (u ^ 0x80) row j's bytes 64 kb + 16 g .. + 15 and stores them at its place in the fragment
 // (one contiguous 1 KiB wave store), keeping int32 partial sums of w and w^2 (|S| <= 2^23, T <= 2^30); the
@@ -1193,30 +1252,9 @@ __global__ __launch_bounds__(1024) void k_cosq_prepare(const uint8_t* __restrict
     const uint8_t* x = X + (r < N ? r : 0) * ld;
     int S = 0, T = 0;
     for (int kb = wv; kb < KB; kb += 16) {
-      const int k0 = kCosqK * kb + 16 * g;
-      uint32_t w[4] = {0u, 0u, 0u, 0u};  // pad rows and pad positions: w = 0
-      if (r < N && k0 < K) {
-        if (fast && k0 + 16 <= K) {
-          const uint4 v = *reinterpret_cast<const uint4*>(x + k0);
-          w[0] = v.x ^ 0x80808080u;
-          w[1] = v.y ^ 0x80808080u;
-          w[2] = v.z ^ 0x80808080u;
-          w[3] = v.w ^ 0x80808080u;
-        } else {
-#pragma unroll
-          for (int u = 0; u < 16; ++u)
-            if (k0 + u < K) w[u >> 2] |= (uint32_t)(x[k0 + u] ^ 0x80u) << (8 * (u & 3));
-        }
-      }
-#pragma unroll
-      for (int d = 0; d < 4; ++d)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-          const int v = (int)(int8_t)(w[d] >> (8 * b));
-          S += v;
-          T += v * v;
-        }
-      *reinterpret_cast<uint4*>(X8 + ((t * KB + kb) * 1024 + 16 * lane)) = make_uint4(w[0], w[1], w[2], w[3]);
+      const uint4 p = cosq_piece(x, kCosqK * kb + 16 * g, K, fast, r < N);  // pad rows and pad positions: w = 0
+      cosq_piece_sums(p, S, T);
+      *reinterpret_cast<uint4*>(X8 + ((t * KB + kb) * 1024 + 16 * lane)) = p;
     }
     S += __shfl_xor(S, 16, 64);
     T += __shfl_xor(T, 16, 64);
@@ -1229,31 +1267,119 @@ __global__ __launch_bounds__(1024) void k_cosq_prepare(const uint8_t* __restrict
     __syncthreads();
     if (threadIdx.x < 16) {
       const int64_t row = 16 * t + threadIdx.x;
-      double A = 0.0, B = 0.0, ok = 0.0;
-      const int64_t Si = sS[threadIdx.x], Ti = sT[threadIdx.x];
-      if (row < N) {
-        const float fmn = mm[2 * row], fmx = mm[2 * row + 1];
-        if (isfinite(fmn) && isfinite(fmx)) {
-          const double mn = fmn, mx = fmx, Kd = K;
-          const double s = mx == mn ? 0.0 : (mx - mn) / 255.0;
-          const double m = mn + s * (128.0 + (double)Si / Kd);
-          const int64_t V = (int64_t)K * Ti - Si * Si;  // >= 0 (Cauchy-Schwarz), below 2^47
-          const double n2 = m * m + (s * s) * ((double)V / (Kd * Kd));  // n^2 / K
-          if (n2 > 0.0) {
-            const double inv = 1.0 / sqrt(n2);
-            A = m * inv;
-            B = (s * inv) / Kd;
-            ok = 1.0;
-          }
-        }
-      }
-      double* o = st + 4 * row;
-      o[0] = A;
-      o[1] = B;
-      o[2] = (double)Si;
-      o[3] = ok;
+      cosq_row_stats(K, sS[threadIdx.x], sT[threadIdx.x], row < N ? mm + 2 * row : nullptr, st + 4 * row);
     }
     __syncthreads();  // sS / sT are cleared for the next tile
+  }
+}
+
+// ---- the mutable store: hq_cosq_append / hq_cosq_replace / hq_cosq_gather ----------------------
+// A row's bytes are 4 KB pieces of 16 bytes, piece (kb, g) at (t KB + kb) 1024 + 16 (16 g + j), and 32 bytes of
+// statistics; no piece holds bytes of two rows and the search kernels mask every row >= N, so rows can be written
+// behind N, in place, or copied to another place one by one, and the result is what k_cosq_prepare writes.
+
+// k_cosq_prepare's tile pass over rows [N0, N1) of a resident operand, tiles N0 / 16 .. rows_out / 16: frame
+// r - N0 of X becomes row r.  Rows below N0 (the leading rows of N0's tile) are neither loaded nor stored, rows
+// [N1, rows_out) are pad rows.  The store is predicated per lane on r >= N0, so every tile but N0's gets
+// k_cosq_prepare's contiguous 1 KiB wave store; a lane sums its own row only, so S and T never see a resident row.
+__global__ __launch_bounds__(1024) void k_cosq_append(const uint8_t* __restrict__ X, int64_t N0, int64_t N1, int64_t ld,
+                                                      int K, int KB, int64_t rows_out, const float* __restrict__ mm,
+                                                      int8_t* __restrict__ X8, double* __restrict__ st, int fast) {
+  __shared__ int sS[16], sT[16];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, j = lane & 15, g = lane >> 4;
+  for (int64_t t = N0 / 16 + blockIdx.x; t < rows_out / 16; t += gridDim.x) {
+    if (threadIdx.x < 16) sS[threadIdx.x] = sT[threadIdx.x] = 0;
+    __syncthreads();
+    const int64_t r = 16 * t + j;
+    const bool live = r >= N0 && r < N1;
+    const uint8_t* x = X + (live ? r - N0 : 0) * ld;
+    int S = 0, T = 0;
+    for (int kb = wv; kb < KB; kb += 16) {
+      const uint4 p = cosq_piece(x, kCosqK * kb + 16 * g, K, fast, live);
+      cosq_piece_sums(p, S, T);
+      if (r >= N0) *reinterpret_cast<uint4*>(X8 + ((t * KB + kb) * 1024 + 16 * lane)) = p;
+    }
+    S += __shfl_xor(S, 16, 64);
+    T += __shfl_xor(T, 16, 64);
+    S += __shfl_xor(S, 32, 64);
+    T += __shfl_xor(T, 32, 64);
+    if (g == 0) {
+      atomicAdd(&sS[j], S);
+      atomicAdd(&sT[j], T);
+    }
+    __syncthreads();
+    if (threadIdx.x < 16) {
+      const int64_t row = 16 * t + threadIdx.x;
+      if (row >= N0)
+        cosq_row_stats(K, sS[threadIdx.x], sT[threadIdx.x], row < N1 ? mm + 2 * (row - N0) : nullptr, st + 4 * row);
+    }
+    __syncthreads();  // sS / sT are cleared for the next tile
+  }
+}
+
+// One 4-wave workgroup per replaced row: thread p takes the row's pieces p, p + 256, .. (piece 4 kb + g: the
+// frame's bytes 16 p .. + 15, read contiguously across the workgroup) and stores each at its lane position of
+// fragment kb; the other 15 rows of the tile are not touched.  A row id outside [0, N) is skipped.
+__global__ __launch_bounds__(256) void k_cosq_replace(const uint8_t* __restrict__ X, int64_t M, int64_t ld, int K, int KB,
+                                                      const float* __restrict__ mm, const int64_t* __restrict__ rows,
+                                                      int64_t N, int8_t* __restrict__ X8, double* __restrict__ st,
+                                                      int fast) {
+  __shared__ int sS, sT;
+  for (int64_t i = blockIdx.x; i < M; i += gridDim.x) {
+    const int64_t row = rows[i];
+    if (row < 0 || row >= N) continue;  // the whole workgroup
+    if (threadIdx.x == 0) sS = sT = 0;
+    __syncthreads();
+    const int64_t t = row >> 4;
+    const int j = (int)(row & 15);
+    const uint8_t* x = X + i * ld;
+    int S = 0, T = 0;
+    for (int p = threadIdx.x; p < 4 * KB; p += 256) {
+      const int kb = p >> 2, g = p & 3;
+      const uint4 v = cosq_piece(x, 16 * p, K, fast, true);
+      cosq_piece_sums(v, S, T);
+      *reinterpret_cast<uint4*>(X8 + ((t * KB + kb) * 1024 + 16 * (16 * g + j))) = v;
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      S += __shfl_xor(S, o, 64);
+      T += __shfl_xor(T, o, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+      atomicAdd(&sS, S);
+      atomicAdd(&sT, T);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) cosq_row_stats(K, sS, sT, mm + 2 * i, st + 4 * row);
+    __syncthreads();  // sS / sT are cleared for the next row
+  }
+}
+
+// One 16-wave workgroup per destination tile, tiles 0 .. rows_out / 16: lane 16 g + j of wave w copies, for the
+// K steps kb = w, w + 16, .., piece (kb, g) of source row src_row[16 t + j] (clamped into [0, N_src) for the
+// load) to its own position: a 16-byte gather load and k_cosq_prepare's contiguous 1 KiB wave store.  Rows
+// [M, rows_out) are pad rows.  Wave 0 copies the sixteen rows' statistics, one float64 per lane.
+__global__ __launch_bounds__(1024) void k_cosq_gather(const int64_t* __restrict__ src_row, int64_t M, int64_t N_src,
+                                                      int KB, int64_t rows_out, const int8_t* __restrict__ X8s,
+                                                      const double* __restrict__ sts, int8_t* __restrict__ X8,
+                                                      double* __restrict__ st) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, j = lane & 15, g = lane >> 4;
+  for (int64_t t = blockIdx.x; t < rows_out / 16; t += gridDim.x) {
+    const int64_t r = 16 * t + j;
+    int64_t s = 0;  // pad rows load nothing (M > 0 implies N_src > 0: hq_cosq_gather's check)
+    if (r < M) s = min(max(src_row[r], (int64_t)0), N_src - 1);
+    const int64_t src = (s >> 4) * KB * 1024 + 16 * (16 * g + (int)(s & 15));
+    for (int kb = wv; kb < KB; kb += 16) {
+      uint4 p = make_uint4(0u, 0u, 0u, 0u);
+      if (r < M) p = *reinterpret_cast<const uint4*>(X8s + (src + (int64_t)kb * 1024));
+      *reinterpret_cast<uint4*>(X8 + ((t * KB + kb) * 1024 + 16 * lane)) = p;
+    }
+    if (threadIdx.x < 64) {  // wave 0, thread 4 i + c: value c of the statistics of the tile's row i
+      const int64_t row = 16 * t + (threadIdx.x >> 2);
+      double v = 0.0;
+      if (row < M) v = sts[4 * min(max(src_row[row], (int64_t)0), N_src - 1) + (threadIdx.x & 3)];
+      st[4 * row + (threadIdx.x & 3)] = v;
+    }
   }
 }
 
@@ -1464,6 +1590,62 @@ int hq_cosq_prepare(const uint8_t* frames, int64_t N, int64_t ld, int K, const f
   const int fast = ((uintptr_t)frames % 16 == 0 && ld % 16 == 0) ? 1 : 0;
   hipLaunchKernelGGL(k_cosq_prepare, dim3((unsigned)blocks), dim3(1024), 0, (hipStream_t)stream, frames, N, ld, K,
                      hq_cosq_padded_k(K) / kCosqK, rows, minmax, reinterpret_cast<int8_t*>(X8), stats, fast);
+  HQ_CHECK_LAUNCH();
+  return HQ_OK;
+}
+
+// cap_rows of a resident operand: whole 128-row units, at least need's padded rows
+static bool cosq_cap_ok(int64_t cap_rows, int64_t need) {
+  return cap_rows >= 0 && cap_rows % kCosT == 0 && need <= cap_rows && hq_cosq_padded_rows(need) <= cap_rows;
+}
+
+int hq_cosq_append(const uint8_t* frames, int64_t M, int64_t ld, int K, const float* minmax, int64_t N0, int64_t cap_rows,
+                   void* X8, double* stats, hq_stream_t stream) {
+  if (M < 0 || N0 < 0 || K <= 0 || ld < K || M > INT64_MAX - N0 || !cosq_cap_ok(cap_rows, N0 + M))
+    return fail(HQ_E_INVALID, "bad shape M=%lld K=%d ld=%lld N0=%lld cap_rows=%lld", (long long)M, K, (long long)ld,
+                (long long)N0, (long long)cap_rows);
+  if (M == 0) return HQ_OK;
+  if (K > kCosqMaxK) return fail(HQ_E_UNSUPPORTED, "K=%d: the int32 accumulator holds K <= %d", K, kCosqMaxK);
+  if (!frames || !minmax || !X8 || !stats) return fail(HQ_E_INVALID, "null buffer");
+  const int64_t rows = hq_cosq_padded_rows(N0 + M);
+  int64_t blocks = rows / 16 - N0 / 16;
+  if (blocks > 65536) blocks = 65536;
+  const int fast = ((uintptr_t)frames % 16 == 0 && ld % 16 == 0) ? 1 : 0;
+  hipLaunchKernelGGL(k_cosq_append, dim3((unsigned)blocks), dim3(1024), 0, (hipStream_t)stream, frames, N0, N0 + M, ld, K,
+                     hq_cosq_padded_k(K) / kCosqK, rows, minmax, reinterpret_cast<int8_t*>(X8), stats, fast);
+  HQ_CHECK_LAUNCH();
+  return HQ_OK;
+}
+
+int hq_cosq_replace(const uint8_t* frames, int64_t M, int64_t ld, int K, const float* minmax, const int64_t* rows,
+                    int64_t N, void* X8, double* stats, hq_stream_t stream) {
+  if (M < 0 || N < 0 || K <= 0 || ld < K)
+    return fail(HQ_E_INVALID, "bad shape M=%lld K=%d ld=%lld N=%lld", (long long)M, K, (long long)ld, (long long)N);
+  if (M == 0) return HQ_OK;
+  if (K > kCosqMaxK) return fail(HQ_E_UNSUPPORTED, "K=%d: the int32 accumulator holds K <= %d", K, kCosqMaxK);
+  if (!frames || !minmax || !rows || !X8 || !stats) return fail(HQ_E_INVALID, "null buffer");
+  const int64_t blocks = M < 65536 ? M : 65536;
+  const int fast = ((uintptr_t)frames % 16 == 0 && ld % 16 == 0) ? 1 : 0;
+  hipLaunchKernelGGL(k_cosq_replace, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, frames, M, ld, K,
+                     hq_cosq_padded_k(K) / kCosqK, minmax, rows, N, reinterpret_cast<int8_t*>(X8), stats, fast);
+  HQ_CHECK_LAUNCH();
+  return HQ_OK;
+}
+
+int hq_cosq_gather(const int64_t* src_row, int64_t M, int64_t N_src, int K, const void* X8_src, const double* stats_src,
+                   int64_t cap_rows, void* X8, double* stats, hq_stream_t stream) {
+  if (M < 0 || N_src < 0 || K <= 0 || (M > 0 && N_src == 0) || !cosq_cap_ok(cap_rows, M))
+    return fail(HQ_E_INVALID, "bad shape M=%lld N_src=%lld K=%d cap_rows=%lld", (long long)M, (long long)N_src, K,
+                (long long)cap_rows);
+  if (M == 0 && cap_rows == 0) return HQ_OK;
+  if (K > kCosqMaxK) return fail(HQ_E_UNSUPPORTED, "K=%d: the int32 accumulator holds K <= %d", K, kCosqMaxK);
+  if ((M > 0 && (!src_row || !X8_src || !stats_src)) || !X8 || !stats) return fail(HQ_E_INVALID, "null buffer");
+  const int64_t rows = M ? hq_cosq_padded_rows(M) : kCosT;  // an empty result: one unit of pad rows
+  int64_t blocks = rows / 16;
+  if (blocks > 65536) blocks = 65536;
+  hipLaunchKernelGGL(k_cosq_gather, dim3((unsigned)blocks), dim3(1024), 0, (hipStream_t)stream, src_row, M, N_src,
+                     hq_cosq_padded_k(K) / kCosqK, rows, reinterpret_cast<const int8_t*>(X8_src), stats_src,
+                     reinterpret_cast<int8_t*>(X8), stats);
   HQ_CHECK_LAUNCH();
   return HQ_OK;
 }

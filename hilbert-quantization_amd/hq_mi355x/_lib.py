@@ -124,6 +124,9 @@ SIGNATURES = {
     "hq_cosq_padded_k": (_i, [_i]),
     "hq_cosq_padded_rows": (_i64, [_i64]),
     "hq_cosq_prepare": (_i, [_p, _i64, _i64, _i, _p, _p, _p, _p]),
+    "hq_cosq_append": (_i, [_p, _i64, _i64, _i, _p, _i64, _i64, _p, _p, _p]),
+    "hq_cosq_replace": (_i, [_p, _i64, _i64, _i, _p, _p, _i64, _p, _p, _p]),
+    "hq_cosq_gather": (_i, [_p, _i64, _i64, _i, _p, _p, _i64, _p, _p, _p]),
     "hq_cosq_scores": (_i, [_p, _p, _i, _p, _p, _i64, _i, _p, _p]),
     "hq_cosq_topk_workspace_size": (_sz, [_i, _i64, _i]),
     "hq_cosq_topk": (_i, [_p, _p, _i, _p, _p, _i64, _i, _i, _d, _i, _i64, _p, _sz, _p, _p, _p]),

@@ -1106,10 +1106,12 @@ class CosQRows:
     operand fragments, stats [Np, 4] f64 (pre-scaled a, b, S, inv != 0): one byte per value resident where the
     split-f16 rows of the decoded frames hold four."""
 
-    __slots__ = ("X8", "stats", "N", "K")
+    __slots__ = ("X8", "stats", "N", "K", "cap")
 
-    def __init__(self, X8, stats, N, K):
+    def __init__(self, X8, stats, N, K, cap=None):
         self.X8, self.stats, self.N, self.K = X8, stats, int(N), int(K)
+        # rows the buffers hold, in whole 128-row units (cosq_reserve / cosq_append / cosq_gather size them)
+        self.cap = int(X8.shape[0]) // 128 * 128 if cap is None else int(cap)
 
     @property
     def nbytes(self) -> int:
@@ -1152,6 +1154,94 @@ def cosq_prepare(frames, minmax, rows: Optional[int] = None, exc=None) -> CosQRo
         _chk(_L().hq_cosq_prepare(ptr(x2), N, x2.stride(0) if N > 1 else int(x2.shape[1]), K, ptr(mm), ptr(X8),
                                   ptr(stats), stream()), exc)
     return CosQRows(X8, stats, N, K)
+
+
+def _rows128(n: int) -> int:
+    return (n + 127) // 128 * 128
+
+
+def _cosq_buffers(cap: int, c: CosQRows):
+    t = torch()
+    X8 = t.empty((max(cap, 1), int(c.X8.shape[1])), dtype=t.int8, device=c.X8.device)
+    stats = t.empty((max(cap, 1), 4), dtype=t.float64, device=c.X8.device)
+    return X8, stats
+
+
+def cosq_reserve(c: CosQRows, capacity: int) -> CosQRows:
+    """A CosQRows of the same N rows whose buffers hold `capacity` rows, rounded up to a multiple of 128 (c itself
+    when they already do): new buffers, device-to-device copies of the valid extent (the padded rows of N).  The
+    rows past it are written by cosq_append."""
+    cap = _rows128(int(capacity))
+    if cap <= c.cap:
+        return c
+    X8, stats = _cosq_buffers(cap, c)
+    Np = _rows128(c.N)
+    X8[:Np].copy_(c.X8[:Np])
+    stats[:Np].copy_(c.stats[:Np])
+    return CosQRows(X8, stats, c.N, c.K, cap)
+
+
+def _cosq_incoming(c: CosQRows, frames, minmax, rows, what: str):
+    """The u8 frames and (min, max) pairs a writer of c takes: (x2 read in place, ld, mm, M)."""
+    t = torch()
+    if frames.dtype != t.uint8:
+        raise TypeError(f"{what} expects uint8 frames")
+    x2, M, K = _frame_rows(frames, rows, "frames", "M")
+    if K != c.K:
+        raise ValueError(f"{what}: frame length {K} != corpus frame length {c.K}")
+    mm = _contig(minmax.reshape(-1, 2).to(t.float32))
+    if int(mm.shape[0]) != M:
+        raise ValueError(f"{int(mm.shape[0])} (min, max) pairs for {M} frames")
+    return x2, (x2.stride(0) if M > 1 else int(x2.shape[1])), mm, M
+
+
+def cosq_append(c: CosQRows, frames, minmax, rows: Optional[int] = None, exc=None) -> CosQRows:
+    """c grown by the u8 `frames` [M, r, c] (or rows [M, K]) with minmax f32 [M, 2] (rows= as cosq_prepare): one
+    hq_cosq_append launch prepares them behind the resident rows, which do not move, and writes the pad rows after
+    them; byte-identical to cosq_prepare of all N + M frames.  Beyond the capacity the buffers grow geometrically
+    (x 2, at least the need: cosq_reserve).  Returns a new CosQRows over the same buffers; c must not be searched
+    afterwards (what it took for pad rows are real rows now), and searches of c still running on other streams
+    must have finished before the call."""
+    x2, ld, mm, M = _cosq_incoming(c, frames, minmax, rows, "cosq_append")
+    if M == 0:
+        return c
+    N0, N1 = c.N, c.N + M
+    if _rows128(N1) > c.cap:
+        c = cosq_reserve(c, max(N1, 2 * c.cap))
+    _chk(_L().hq_cosq_append(ptr(x2), M, ld, c.K, ptr(mm), N0, c.cap, ptr(c.X8), ptr(c.stats), stream()), exc)
+    return CosQRows(c.X8, c.stats, N1, c.K, c.cap)
+
+
+def cosq_replace(c: CosQRows, row_ids, frames, minmax, rows: Optional[int] = None, checked: bool = False,
+                 exc=None) -> CosQRows:
+    """c with the resident rows `row_ids` (distinct row numbers in [0, c.N)) overwritten in place by the u8 `frames`
+    [M, r, c] (or rows [M, K]) with minmax f32 [M, 2]: one hq_cosq_replace launch rewrites those rows' bytes and
+    statistics; byte-identical to cosq_prepare of the updated frames.  A writer, as cosq_append: no search of c may
+    be running.  Returns c.  IndexError for a row out of range, ValueError for a repeated row, before any launch
+    (checked: the caller has validated the row numbers)."""
+    t = torch()
+    x2, ld, mm, M = _cosq_incoming(c, frames, minmax, rows, "cosq_replace")
+    sel = _row_ids(row_ids, c.N, x2.device, "cosq_replace", checked)
+    if int(sel.numel()) != M:
+        raise ValueError(f"{int(sel.numel())} row numbers for {M} replacement frames")
+    if not checked and M > 1 and int(t.unique(sel).numel()) != M:
+        raise ValueError("cosq_replace: repeated row numbers")
+    if M:
+        _chk(_L().hq_cosq_replace(ptr(x2), M, ld, c.K, ptr(mm), ptr(sel), c.N, ptr(c.X8), ptr(c.stats), stream()), exc)
+    return c
+
+
+def cosq_gather(c: CosQRows, src_rows, cap: Optional[int] = None, checked: bool = False, exc=None) -> CosQRows:
+    """A new CosQRows of the rows c[src_rows] (row numbers in [0, c.N), any order, repeats allowed), in a second
+    pair of buffers with room for max(cap or c.cap, M) rows (a multiple of 128): one hq_cosq_gather launch moves
+    each row's 16-byte pieces and statistics, byte-identical to cosq_prepare of the selected frames.  c is only
+    read.  IndexError for a row out of range, before the launch (checked: the caller has validated them)."""
+    sel = _row_ids(src_rows, c.N, c.X8.device, "cosq_gather", checked)
+    M = int(sel.numel())
+    cap = max(_rows128(int(cap) if cap else c.cap), _rows128(M))
+    X8, stats = _cosq_buffers(cap, c)
+    _chk(_L().hq_cosq_gather(ptr(sel), M, c.N, c.K, ptr(c.X8), ptr(c.stats), cap, ptr(X8), ptr(stats), stream()), exc)
+    return CosQRows(X8, stats, M, c.K, cap)
 
 
 def cosq_scores(q: CosQRows, c: CosQRows, exc=None):

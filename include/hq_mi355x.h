@@ -630,6 +630,41 @@ int hq_cosq_topk(const void* A8, const double* stats_a, int Q, const void* B8, c
                  int K, int k, double threshold, int thr_mode, int64_t id_base,
                  void* workspace, size_t workspace_bytes,
                  double* out_score, int64_t* out_id, hq_stream_t stream);
+/* The mutable store.  A resident operand (X8, stats) may hold more rows than its N frames need: cap_rows rows, a
+ *   multiple of 128 and >= hq_cosq_padded_rows(N).  hq_cosq_scores / hq_cosq_topk / hq_cosqf_scores / hq_cosqf_topk
+ *   read only the first hq_cosq_padded_rows(N) rows and mask every frame >= N, so such a buffer is a valid operand
+ *   as it stands.  A row's bytes are 4 KB pieces of 16 bytes (KB = hq_cosq_padded_k(K) / 64), piece (kb, g) at
+ *   (t KB + kb) 1024 + 16 (16 g + j) for row 16 t + j, and 32 bytes of stats: no piece holds bytes of two rows.
+ *   The contract of the three calls below: afterwards the first hq_cosq_padded_rows(N) rows of X8 and of stats,
+ *   N the resulting number of frames, equal bit for bit what hq_cosq_prepare writes for those N frames (pad rows
+ *   [N, padded rows) included: bytes 0, stats (0, 0, 0, 0)); nothing past them is written and no row the call
+ *   does not name changes.  All three are writers of (X8, stats): the caller orders them after every search
+ *   that reads the corpus (stream order or an event), as for hq_seg_append.
+ * hq_cosq_append: grow a resident operand of N0 frames by the M frames of `frames` (u8, ld bytes apart, minmax f32
+ *   [M, 2], as hq_cosq_prepare) in ONE launch: frame i becomes row N0 + i.  In N0's 16-row tile only the pieces
+ *   and stats of rows >= N0 are written and the sums S and T run over the new rows alone; every further tile is
+ *   hq_cosq_prepare's contiguous 1 KiB wave store per fragment (16-byte loads when the base and ld are multiples
+ *   of 16, byte loads otherwise).  Rows [N0 + M, hq_cosq_padded_rows(N0 + M)) are written as pad rows (after a
+ *   reallocation they are uninitialised memory).  cap_rows >= hq_cosq_padded_rows(N0 + M).
+ * hq_cosq_replace: overwrite M resident rows of a corpus of N frames IN PLACE in ONE launch: frame i takes row
+ *   rows[i] (device int64 [M], distinct values in [0, N): the caller's precondition), bytes and stats; the other
+ *   rows of its tile keep their bytes.  A row id outside [0, N) is skipped, not written.
+ * hq_cosq_gather: row i of a SECOND operand (X8, stats; cap_rows rows; it may not alias the source) becomes row
+ *   src_row[i] of the source of N_src frames (device int64 [M], any order, repeats allowed) in ONE launch.
+ *   Nothing is recomputed: the 4 KB pieces move to their new lane positions (destination tiles as whole 1 KiB
+ *   wave stores) and the 32 stats bytes with them; rows [M, hq_cosq_padded_rows(M)) are written as pad rows.  An
+ *   id outside [0, N_src) is clamped for the load: that row's content is unspecified, no read leaves the source.
+ *   Removing, selecting, inserting and re-ordering frames are all this call.  cap_rows >= hq_cosq_padded_rows(M).
+ * Return codes, in hq_cosq_prepare's order: negative sizes, K < 1, ld < K, cap_rows not a multiple of 128 or
+ *   smaller than the result's padded rows, M > 0 with N_src = 0: HQ_E_INVALID; then M = 0: HQ_OK and nothing is
+ *   touched (hq_cosq_gather with M = 0 and cap_rows > 0 goes on and writes rows [0, 128) as the pad rows of an
+ *   empty corpus); K > 65536: HQ_E_UNSUPPORTED; a NULL buffer: HQ_E_INVALID.                                  */
+int hq_cosq_append(const uint8_t* frames, int64_t M, int64_t ld, int K, const float* minmax, int64_t N0,
+                   int64_t cap_rows, void* X8, double* stats, hq_stream_t stream);
+int hq_cosq_replace(const uint8_t* frames, int64_t M, int64_t ld, int K, const float* minmax, const int64_t* rows,
+                    int64_t N, void* X8, double* stats, hq_stream_t stream);
+int hq_cosq_gather(const int64_t* src_row, int64_t M, int64_t N_src, int K, const void* X8_src,
+                   const double* stats_src, int64_t cap_rows, void* X8, double* stats, hq_stream_t stream);
 
 /* ---- float32 queries against the u8 frame store: exact asymmetric cosine top-k --------------------
  * The corpus stays compressed (exactly what hq_cosq_prepare wrote: one resident corpus serves both query kinds),
