@@ -98,8 +98,11 @@ static void trad_plan(int n, int L, TradPlan& p) {
   p.produced = out;
 }
 
-// value of output slot i of the traditional index for an n x n f32 image with leading dim ld
-__device__ float trad_slot(const float* img, int n, int ld, const TradPlan& p, int i) {
+// value of output slot i of the traditional index for an n x n image (f32 or f64) with leading dim ld:
+// means and samples in the image dtype, cast to float32 at the return (the reference's final
+// np.array(..., dtype=np.float32), core/index_generator.py:346)
+template <typename T>
+__device__ float trad_slot(const T* img, int n, int ld, const TradPlan& p, int i) {
   if (i >= p.produced) return 0.f;
   for (int e = 0; e < p.cnt; ++e) {
     if (i >= p.first[e] + p.count[e]) continue;
@@ -107,9 +110,9 @@ __device__ float trad_slot(const float* img, int n, int ld, const TradPlan& p, i
     int g = p.grid[e];
     if (!p.sampling[e]) {
       int sh = n / g;
-      if (sh == 0) return np_mean_block(img, n, ld, n);
+      if (sh == 0) return (float)np_mean_block(img, n, ld, n);
       int r = k / g, c = k % g;
-      return np_mean_block(img + (r * sh) * ld + c * sh, sh, ld, sh);
+      return (float)np_mean_block(img + (r * sh) * ld + c * sh, sh, ld, sh);
     }
     int sec = n / g;
     if (sec < 1) sec = 1;
@@ -117,31 +120,32 @@ __device__ float trad_slot(const float* img, int n, int ld, const TradPlan& p, i
     if (sy == 0) {
       const int h = n, w = n;
       switch (k) {
-        case 0: return img[0];
-        case 1: return img[w - 1];
-        case 2: return img[(h - 1) * ld];
-        case 3: return img[(h - 1) * ld + w - 1];
-        default: return img[(h / 2) * ld + w / 2];
+        case 0: return (float)img[0];
+        case 1: return (float)img[w - 1];
+        case 2: return (float)img[(h - 1) * ld];
+        case 3: return (float)img[(h - 1) * ld + w - 1];
+        default: return (float)img[(h / 2) * ld + w / 2];
       }
     }
     int s = k / 5, which = k % 5;
     int r = s / sy, c = s % sy;  // sections visited row-major (sections_x == sections_y)
     int r0 = r * sec, r1 = r0 + sec, c0 = c * sec, c1 = c0 + sec;
     switch (which) {
-      case 0: return img[r0 * ld + c0];
-      case 1: return img[r0 * ld + c1 - 1];
-      case 2: return img[(r1 - 1) * ld + c0];
-      case 3: return img[(r1 - 1) * ld + c1 - 1];
-      default: return img[((r0 + r1) / 2) * ld + (c0 + c1) / 2];
+      case 0: return (float)img[r0 * ld + c0];
+      case 1: return (float)img[r0 * ld + c1 - 1];
+      case 2: return (float)img[(r1 - 1) * ld + c0];
+      case 3: return (float)img[(r1 - 1) * ld + c1 - 1];
+      default: return (float)img[((r0 + r1) / 2) * ld + (c0 + c1) / 2];
     }
   }
   return 0.f;
 }
 
-__global__ __launch_bounds__(64) void k_trad_image(const float* __restrict__ img, int64_t N, int n, int L,
+template <typename T>
+__global__ __launch_bounds__(64) void k_trad_image(const T* __restrict__ img, int64_t N, int n, int L,
                                                    TradPlan plan, float* __restrict__ out) {
   for (int64_t e = blockIdx.x; e < N; e += gridDim.x) {
-    const float* im = img + e * (int64_t)n * n;
+    const T* im = img + e * (int64_t)n * n;
     for (int i = threadIdx.x; i < L; i += 64) out[e * (int64_t)L + i] = trad_slot(im, n, n, plan, i);
   }
 }
@@ -659,17 +663,29 @@ using namespace hq;
 
 extern "C" {
 
-int hq_index_traditional_f32(const float* img, int64_t N, int n, int L, float* out, hq_stream_t stream) {
+int hq_index_traditional(int dtype, const void* img, int64_t N, int n, int L, float* out, hq_stream_t stream) {
+  if (dtype != HQ_F32 && dtype != HQ_F64) return fail(HQ_E_UNSUPPORTED, "traditional index dtype %d (f32/f64)", dtype);
   if (!is_pow2(n)) return fail(HQ_E_NOT_POW2, "Dimension must be a power of 2, got %d", n);
   if (N < 0 || L < 0) return fail(HQ_E_INVALID, "bad shape");
   if (N == 0 || L == 0) return HQ_OK;
   if (!img || !out) return fail(HQ_E_INVALID, "null buffer");
   TradPlan plan;
   trad_plan(n, L, plan);
-  int grid = persistent_grid((const void*)k_trad_image, 64, 0, N);
-  hipLaunchKernelGGL(k_trad_image, dim3(grid), dim3(64), 0, (hipStream_t)stream, img, N, n, L, plan, out);
+  if (dtype == HQ_F32) {
+    int grid = persistent_grid((const void*)k_trad_image<float>, 64, 0, N);
+    hipLaunchKernelGGL(k_trad_image<float>, dim3(grid), dim3(64), 0, (hipStream_t)stream, (const float*)img, N, n, L,
+                       plan, out);
+  } else {
+    int grid = persistent_grid((const void*)k_trad_image<double>, 64, 0, N);
+    hipLaunchKernelGGL(k_trad_image<double>, dim3(grid), dim3(64), 0, (hipStream_t)stream, (const double*)img, N, n,
+                       L, plan, out);
+  }
   HQ_CHECK_LAUNCH();
   return HQ_OK;
+}
+
+int hq_index_traditional_f32(const float* img, int64_t N, int n, int L, float* out, hq_stream_t stream) {
+  return hq_index_traditional(HQ_F32, img, N, n, L, out, stream);
 }
 
 int hq_block_means(int dtype, const void* img, int64_t N, int n, int grid, int order, void* out,

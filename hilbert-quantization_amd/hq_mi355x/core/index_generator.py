@@ -2,8 +2,8 @@
 
 Drop-in for the reference's core/index_generator.py:13-356: `use_streaming_optimization` selects the
 streaming index (hq_index_streaming), otherwise the traditional block-mean/offset-sample index
-(hq_index_traditional_f32, including the is_offset_sampling quirk of :329-332).  Allocation tables
-are host-side integer logic, identical to :34-98.
+(hq_index_traditional, including the is_offset_sampling quirk of :329-332; float64 images are averaged
+in float64, as np.mean does).  Allocation tables are host-side integer logic, identical to :34-98.
 """
 from __future__ import annotations
 
@@ -118,9 +118,13 @@ class HierarchicalIndexGeneratorImpl(*_bases("interfaces", "HierarchicalIndexGen
         return self._generate_traditional_indices(image, index_space_size)
 
     def _generate_traditional_indices(self, image, index_space_size: int):
+        if not level_allocation(int(index_space_size)):
+            return np.array([])  # an empty allocation (index_space_size == 1): float64, shape (0,) (:318-319)
         if is_tensor(image):
             return K.index_traditional(to_dev(image), int(index_space_size))
-        img = np.asarray(image, dtype=np.float32)
+        img = np.asarray(image)
+        if img.dtype not in (np.float32, np.float64):
+            img = img.astype(np.float64)
         h, w = img.shape
         if h != w or (w & (w - 1)) != 0:
             raise ValueError(f"traditional index on the GPU needs a square power-of-2 image, got {w}x{h}")

@@ -91,13 +91,20 @@ def index_streaming(img, L: int, stream_len: Optional[int] = None, exc=None):
 
 
 def index_traditional(img, L: int, exc=None):
-    """Traditional index of [N, n, n] f32 images -> f32 [N, L] (core/index_generator.py:313-356)."""
+    """Traditional index of [N, n, n] f32/f64 images -> f32 [N, L] (core/index_generator.py:313-356).
+    Float64 images are averaged and sampled in float64 and rounded to float32 once per slot, as the
+    reference does; any other dtype is widened to float64 first.  Slots the level allocation does not
+    fill stay 0.0: at L = 1 the allocation is empty, so the row is [0.0] (the reference returns an empty
+    array there; core.HierarchicalIndexGeneratorImpl.generate_optimized_indices reproduces that)."""
     t = torch()
     squeeze = img.dim() == 2
-    im = _contig((img.unsqueeze(0) if squeeze else img).to(t.float32))
+    im = img.unsqueeze(0) if squeeze else img
+    if im.dtype not in (t.float32, t.float64):
+        im = im.to(t.float64)
+    im = _contig(im)
     N, n, _ = im.shape
     out = t.zeros((N, L), dtype=t.float32, device=im.device)
-    _chk(_L().hq_index_traditional_f32(ptr(im), N, n, L, ptr(out), stream()), exc)
+    _chk(_L().hq_index_traditional(dtype_code(im.dtype), ptr(im), N, n, L, ptr(out), stream()), exc)
     return out[0] if squeeze else out
 
 

@@ -117,6 +117,11 @@ int hq_index_streaming(int dtype, const void* img, int64_t N, int n, int stream_
  * encoder, core/streaming_processor.py:858-860,897-899).  img: f32 N x n x n; out: f32 N x L.   */
 int hq_index_traditional_f32(const float* img, int64_t N, int n, int L, float* out,
                              hq_stream_t stream);
+/* The same index for images of dtype HQ_F32 or HQ_F64.  A float64 image keeps the reference's
+ * arithmetic: block means are np.mean in float64 (pairwise sum / count), samples are read in
+ * float64, and every slot is rounded to float32 once, at the store (:346).                      */
+int hq_index_traditional(int dtype, const void* img, int64_t N, int n, int L, float* out,
+                         hq_stream_t stream);
 
 /* ---- I2/I4 building block: block means ---------------------------------------------------------
  * np.mean of each (n/grid)^2 block of N x n x n images (dtype HQ_F32 or HQ_F64, NumPy pairwise

@@ -738,6 +738,108 @@ def sortkey_fixtures(hq):
     return out
 
 
+def index_sweep_fixtures(hq):
+    """Sweep of the index generators over every branch of the slot plan (tests/index_sweep_cases.py): traditional
+    and streaming index of every image at every L in LS as 8-byte digests (full arrays at LS_FULL, the
+    exception's class name where the reference raises), padded streams through generate_indices_during_mapping,
+    the RAG generator's index rows and calculate_spatial_averages at dividing, non-dividing and too-large grids."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import index_sweep_cases as S
+    from hilbert_quantization.core.streaming_index_builder import StreamingHilbertIndexGenerator
+    from hilbert_quantization.core.index_generator import HierarchicalIndexGeneratorImpl
+    from hilbert_quantization.rag.embedding_generation.hierarchical_index_generator import (
+        HierarchicalIndexGenerator as RagGen)
+    sg = StreamingHilbertIndexGenerator()
+    tg = HierarchicalIndexGeneratorImpl()
+    rg = RagGen()
+    out = {"LS": np.array(S.LS, dtype=np.int64), "LS_FULL": np.array(S.LS_FULL, dtype=np.int64)}
+
+    def record(fn, key, L, digs, errs):
+        try:
+            v = np.asarray(fn())
+            digs.append(S.digest_row(v))
+            errs.append("")
+            if L in S.LS_FULL:
+                out[f"{key}_L{L}"] = v
+        except Exception as e:  # noqa: BLE001
+            digs.append(np.zeros(8, np.uint8))
+            errs.append(type(e).__name__)
+
+    images = S.make_images()
+    for (kind, n), img in images.items():
+        tag = f"{kind}_n{n}"
+        out[f"img_{tag}"] = img
+        for name, gen in (("trad", tg), ("strm", sg)):
+            digs, errs = [], []
+            for L in S.LS:
+                record(lambda: gen.generate_optimized_indices(img, L), f"{name}_{tag}", L, digs, errs)
+            out[f"{name}_dig_{tag}"] = np.stack(digs)
+            out[f"{name}_err_{tag}"] = np.array(errs)
+    for (n, d), p in S.make_padded_params().items():
+        out[f"pad_params_n{n}_d{d}"] = p
+        digs, errs = [], []
+        for L in S.padded_ls(n):
+            record(lambda: sg.generate_indices_during_mapping(p, (n, n), L)[1], f"pad_n{n}_d{d}", -1, digs, errs)
+        out[f"pad_dig_n{n}_d{d}"] = np.stack(digs)
+        out[f"pad_err_n{n}_d{d}"] = np.array(errs)
+        out[f"pad_img_dig_n{n}_d{d}"] = S.digest_row(sg.generate_indices_during_mapping(p, (n, n), n)[0])
+    for n in S.RAG_SIDES_F32:
+        img = images[("f32", n)] if n <= 128 else S.image_256(images[("f32", 128)])
+        out[f"rag_rows_f32_n{n}"] = np.asarray(rg.generate_multi_level_indices(img))[n:]
+    for n in S.SIDES_F64:
+        out[f"rag_rows_f64_n{n}"] = np.asarray(rg.generate_multi_level_indices(images[("f64", n)]))[n:]
+    for kind, n in S.BLOCK_IMAGES:
+        for g in S.GRIDS:
+            out[f"block_{kind}_n{n}_g{g}"] = np.array(tg.calculate_spatial_averages(images[(kind, n)], g))
+    return out
+
+
+def precomp_sim_fixtures(hq):
+    """The pre-computed similarity scorer (core/precomputed_hilbert_index.py:358-496) on the cases of
+    tests/precomp_sim_cases.py: value (float64) and result type (0 numpy float32, 1 Python float) of
+    _compare_precomputed_levels and _calculate_precomputed_similarity, the legacy compare_indices_at_level, and a
+    digest of every input so the seeded cases cannot drift unnoticed."""
+    import warnings
+    sys.path.insert(0, os.path.dirname(HERE))
+    import precomp_sim_cases as P
+    from hilbert_quantization.core.precomputed_hilbert_index import (
+        PrecomputedHilbertIndexer, PrecomputedIndex, PrecomputedLevel, PrecomputedSimilaritySearchEngine)
+    eng = PrecomputedSimilaritySearchEngine(PrecomputedHilbertIndexer())
+    lv = lambda a: PrecomputedLevel(2, 2, len(a), a, [])  # noqa: E731
+    ix = lambda levels: PrecomputedIndex("x", (0, 0), [lv(a) for a in levels], 0.0, 0)  # noqa: E731
+    out = {}
+    warnings.simplefilter("ignore")
+    with np.errstate(all="ignore"):
+        cases = P.single_level_cases()
+        res = [eng._compare_precomputed_levels(lv(q), lv(c)) for (_, q, c) in cases]
+        out["single_names"] = np.array([n for (n, _, _) in cases])
+        out["single_value"] = np.array([float(v) for v in res], dtype=np.float64)
+        out["single_type"] = np.array([P.type_code(v) for v in res], dtype=np.uint8)
+        out["single_digest"] = np.stack([np.frombuffer(P.digest(q) + P.digest(c), np.uint8) for (_, q, c) in cases])
+        cases = P.legacy_cases()
+        res = [eng.compare_indices_at_level(q, c, 0) for (_, q, c) in cases]
+        out["legacy_names"] = np.array([n for (n, _, _) in cases])
+        out["legacy_value"] = np.array([float(v) for v in res], dtype=np.float64)
+        out["legacy_digest"] = np.stack([np.frombuffer(P.digest(q) + P.digest(c), np.uint8) for (_, q, c) in cases])
+        for name, (Q, C) in P.multi_level_cases().items():
+            nl = min(len(Q[0]), len(C[0]))
+            ov = np.zeros((len(Q), len(C)))
+            ty = np.zeros((len(Q), len(C)), np.uint8)
+            ls = np.zeros((len(Q), len(C), nl))
+            lt = np.zeros((len(Q), len(C), nl), np.uint8)
+            for a, q in enumerate(Q):
+                for b, c in enumerate(C):
+                    v = eng._calculate_precomputed_similarity(ix(q), ix(c))
+                    ov[a, b], ty[a, b] = float(v), P.type_code(v)
+                    for l in range(nl):
+                        v = eng._compare_precomputed_levels(lv(q[l]), lv(c[l]))
+                        ls[a, b, l], lt[a, b, l] = float(v), P.type_code(v)
+            out[f"multi_{name}_overall"], out[f"multi_{name}_type"] = ov, ty
+            out[f"multi_{name}_levels"], out[f"multi_{name}_ltype"] = ls, lt
+            out[f"multi_{name}_digest"] = np.stack([np.frombuffer(P.digest(P.pack(x)[0]), np.uint8) for x in Q + C])
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref", default="/root/reference")
@@ -749,7 +851,8 @@ def main():
                      ("search", search_fixtures), ("search_f32", search_f32_fixtures),
                      ("rag_score", rag_score_fixtures), ("stores", store_fixtures),
                      ("precomputed", precomputed_fixtures), ("api", api_fixtures),
-                     ("sortkey", sortkey_fixtures)]:
+                     ("sortkey", sortkey_fixtures), ("index_sweep", index_sweep_fixtures),
+                     ("precomp_sim", precomp_sim_fixtures)]:
         if only and name not in only:
             continue
         d = fn(hq)
