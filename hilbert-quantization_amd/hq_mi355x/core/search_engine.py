@@ -1117,6 +1117,11 @@ class ProgressiveSimilaritySearchEngine(*_bases("interfaces", "SimilaritySearchE
         if len(query_indices) == 0 or not candidate_pool:
             return []
         q = _idx(query_indices)
+        if not self._parse_index_structure(q, len(q)):
+            # no level structure (a one-value index): the reference scores every candidate 0.0 (:206-207) and its
+            # stable sort keeps the pool order; the kernels refuse such a length
+            n = max(0, min(int(max_results), len(candidate_pool)))
+            return self._results(candidate_pool, np.arange(n), np.zeros(n), np.zeros((n, 0)), with_error=False)
         if self._uniform(q, candidate_pool):
             corpus = self._pool_acquire(candidate_pool)
             try:

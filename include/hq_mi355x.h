@@ -296,6 +296,8 @@ int hq_scan_topk(const double* Zq, const double* Sq, int Q, const double* Zc, co
  * per row, the same arithmetic and outputs as the two calls; L <= 4096, level-0 segment <= 32 values).  */
 int hq_seg_prepare_pack0(const double* idx, int64_t N, int L, int src_f32, const uint8_t* row_f32, double* Z,
                          double* stats, void* Z16, float* S32, hq_stream_t stream);
+/* The level-0 segment's PADDED length (its values rounded up to a multiple of 4: the columns the scans
+ * contract over), 0 when L has no level structure (L = 1). */
 int hq_seg_level0_len(int L);
 int hq_seg_pack0_split(const double* Z, const double* S, int64_t N, int L, void* Z16, float* S32,
                        hq_stream_t stream);
@@ -389,7 +391,11 @@ int hq_scanov_topk_split(const void* Zq16, const float* Sq32, const double* Sq, 
  * top-k (score desc, id asc): out_score/out_id Q x k, out_count Q, and out_resolved Q = 1 when the
  * result is provably the exact top-k over the whole corpus given |approx - exact| <= eps (else the
  * caller re-runs that query on the dense exact path).  kp <= 1024 (lists longer than 64 are staged in
- * tiles and ranked by an LDS sort; even L), k <= kp.  out_redo (device int, may
+ * tiles and ranked by an LDS sort), k <= kp.  Any L with a level structure (L >= 2): the lane-cooperative
+ * kernels take even L <= 140 (every segment <= 128 values, at most six levels), the LDS-staged kernel even L
+ * whose kp rows fit 96 KiB (L <= 160 at kp = 64), every other length - odd L included - kernels that read
+ * the rows from global memory; the outputs are the same, bit for bit (tests/test_gpu_scorer_sweep.py runs
+ * every one of them against the CPU oracle).  out_redo (device int, may
  * be NULL): the number of queries that need the dense path — unresolved, or (count_empty != 0) with
  * no candidate passing — so the caller syncs on one int.                                          */
 int hq_refine_topk(const double* Rq, const double* Zq, const double* Sq, int Q, const double* Rc,

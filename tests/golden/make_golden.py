@@ -840,6 +840,83 @@ def precomp_sim_fixtures(hq):
     return out
 
 
+def scorer_sweep_fixtures(hq):
+    """The exact scorers over the index-length sweep of tests/scorer_sweep_cases.py, run by the reference itself:
+    compare_indices_at_level at every level and at level == nseg, and _calculate_overall_similarity, for every
+    length and dtype combination as an 8-byte digest of the value table (float64 [6, 24, nseg + 2]) and of the
+    result-type table (1: numpy float32), full tables at LS_FULL; progressive_search (M = 20 on pools of 40) and
+    brute_force_search at one length per routing class, ids and scores in full; a digest of every length's
+    inputs.  L = 1: what the reference returns where the level structure is empty."""
+    import warnings
+    sys.path[:0] = [os.path.dirname(HERE), os.path.dirname(os.path.dirname(HERE))]
+    import scorer_sweep_cases as S
+    from hilbert_quantization.core.search_engine import ProgressiveSimilaritySearchEngine
+    from hilbert_quantization.models import ModelMetadata, QuantizedModel
+    eng = ProgressiveSimilaritySearchEngine(similarity_threshold=0.1, max_candidates_per_level=S.M_GOLDEN)
+    out = {"LS": np.array(S.LS, dtype=np.int64), "LS_FULL": np.array(S.LS_FULL, dtype=np.int64),
+           "LS_SEARCH": np.array(S.LS_SEARCH, dtype=np.int64)}
+    warnings.simplefilter("ignore")
+
+    def models_of(rows):
+        return [QuantizedModel(b"x", (8, 8), 1, 0.8, r, ModelMetadata(f"m{b}", 1, 1, 1.0, "t"))
+                for b, r in enumerate(rows)]
+
+    with np.errstate(all="ignore"):
+        in_dig = []
+        digs = {c: ([], []) for c in S.COMBOS}
+        for L in S.LS:
+            rows = S.make_rows(L)
+            in_dig.append(S.inputs_digest(rows))
+            nseg = len(eng._parse_index_structure(rows["Q64"][0], L))
+            for combo in S.COMBOS:
+                Q, cand = S.combo_inputs(rows, combo)
+                val = np.zeros((len(Q), len(cand), nseg + 2))
+                ty = np.zeros(val.shape, np.uint8)
+                for a, q in enumerate(Q):
+                    for b, c in enumerate(cand):
+                        res = [eng.compare_indices_at_level(q, c, lv) for lv in range(nseg + 1)]
+                        res.append(eng._calculate_overall_similarity(q, c)[0])
+                        val[a, b] = [float(v) for v in res]
+                        ty[a, b] = [isinstance(v, np.float32) for v in res]
+                digs[combo][0].append(S.digest_row(val))
+                digs[combo][1].append(S.digest_row(ty))
+                if L in S.LS_FULL:
+                    out[f"val_{combo}_L{L}"], out[f"type_{combo}_L{L}"] = val, ty
+        out["inputs_dig"] = np.stack(in_dig)
+        out["parse_struct"] = np.array([(L, lv.grid_size, lv.start_index, lv.end_index, int(lv.is_offset_sampling))
+                                        for L in [1] + S.LS for lv in eng._parse_index_structure(np.zeros(L), L)],
+                                       dtype=np.int64)
+        for combo in S.COMBOS:
+            out[f"val_dig_{combo}"], out[f"type_dig_{combo}"] = np.stack(digs[combo][0]), np.stack(digs[combo][1])
+        pin = []
+        for L in S.LS_SEARCH:
+            pool = S.make_pool(L)
+            pin.append(S.inputs_digest(pool))
+            for ptag, (Q, cand) in (("p64", (pool["Q64"], list(pool["C64"]))), ("p32", (pool["Q32"], list(pool["C32"]))),
+                                    ("pmix", S.combo_inputs(pool, "mix"))):
+                models = models_of(cand)
+                for stag, fn in (("bf", eng.brute_force_search), ("pg", eng.progressive_search)):
+                    ids = np.full((len(Q), S.TOP_K), -1, np.int64)
+                    sc = np.zeros((len(Q), S.TOP_K))
+                    for a in range(len(Q)):
+                        for j, x in enumerate(fn(Q[a], models, S.TOP_K)):
+                            ids[a, j] = int(x.model.model_id[1:])
+                            sc[a, j] = float(x.similarity_score)
+                    out[f"{stag}_ids_{ptag}_L{L}"], out[f"{stag}_sc_{ptag}_L{L}"] = ids, sc
+        out["pool_dig"] = np.stack(pin)
+        # L = 1: no level structure
+        one = np.array([0.5])
+        out["L1_nlevels"] = np.array(len(eng._parse_index_structure(one, 1)), dtype=np.int64)
+        out["L1_level0"] = np.array(float(eng.compare_indices_at_level(one, one, 0)))
+        out["L1_overall"] = np.array(float(eng._calculate_overall_similarity(one, one)[0]))
+        m1 = models_of([np.array([0.5]), np.array([0.25]), np.array([0.5])])
+        out["L1_pg_count"] = np.array(len(eng.progressive_search(one, m1, 10)), dtype=np.int64)
+        out["L1_bf_ids"] = np.array([int(x.model.model_id[1:]) for x in eng.brute_force_search(one, m1, 10)],
+                                    dtype=np.int64)
+        out["L1_bf_sc"] = np.array([float(x.similarity_score) for x in eng.brute_force_search(one, m1, 10)])
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref", default="/root/reference")
@@ -852,7 +929,7 @@ def main():
                      ("rag_score", rag_score_fixtures), ("stores", store_fixtures),
                      ("precomputed", precomputed_fixtures), ("api", api_fixtures),
                      ("sortkey", sortkey_fixtures), ("index_sweep", index_sweep_fixtures),
-                     ("precomp_sim", precomp_sim_fixtures)]:
+                     ("precomp_sim", precomp_sim_fixtures), ("scorer_sweep", scorer_sweep_fixtures)]:
         if only and name not in only:
             continue
         d = fn(hq)
