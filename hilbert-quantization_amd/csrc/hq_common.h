@@ -335,6 +335,28 @@ struct Sum2 {
   __device__ __forceinline__ Sum2 operator+(const Sum2& o) const { return Sum2(a + o.a, b + o.b); }
 };
 
+// ------------------------------------------------------------------------------------------------
+// RAG engine, shared by hq_rag.hip and hq_comp.hip
+// ------------------------------------------------------------------------------------------------
+// _detect_original_embedding_height (engine.py:134-162): from the bottom row up, the first row whose zero
+// ratio np.sum(row == 0) / W is below 0.5 ends the original embedding (height = row + 1); H if none.
+// zeros / W < 0.5 <=> 2 zeros < W exactly (W < 2^24: the quotient is never within an ulp of 0.5).
+// Block-cooperative: every thread takes rows, the largest qualifying row wins (LDS atomicMax).
+template <typename T>
+__device__ int detect_height(const T* img, int H, int W, int* slot) {
+  if (threadIdx.x == 0) *slot = 0;
+  __syncthreads();
+  for (int r = threadIdx.x; r < H; r += blockDim.x) {
+    int z = 0;
+    for (int c = 0; c < W; ++c) z += img[(int64_t)r * W + c] == (T)0 ? 1 : 0;
+    if (2 * z < W) atomicMax(slot, r + 1);
+  }
+  __syncthreads();
+  const int h = *slot;
+  __syncthreads();
+  return h > 0 ? h : H;
+}
+
 // element size of an HQ dtype code (0 if unknown)
 inline int dtype_size(int dt) {
   switch (dt) {

@@ -31,25 +31,6 @@ __global__ __launch_bounds__(256) void k_cosine_t(const T* __restrict__ A, int Q
   }
 }
 
-// _detect_original_embedding_height (engine.py:134-162): from the bottom row up, the first row whose zero
-// ratio np.sum(row == 0) / W is below 0.5 ends the original embedding (height = row + 1); H if none.
-// zeros / W < 0.5 <=> 2 zeros < W exactly (W < 2^24: the quotient is never within an ulp of 0.5).
-// Block-cooperative: every thread takes rows, the largest qualifying row wins (LDS atomicMax).
-template <typename T>
-__device__ int detect_height(const T* img, int H, int W, int* slot) {
-  if (threadIdx.x == 0) *slot = 0;
-  __syncthreads();
-  for (int r = threadIdx.x; r < H; r += blockDim.x) {
-    int z = 0;
-    for (int c = 0; c < W; ++c) z += img[(int64_t)r * W + c] == (T)0 ? 1 : 0;
-    if (2 * z < W) atomicMax(slot, r + 1);
-  }
-  __syncthreads();
-  const int h = *slot;
-  __syncthreads();
-  return h > 0 ? h : H;
-}
-
 template <typename T>
 __global__ __launch_bounds__(64) void k_detect_heights(const T* __restrict__ imgs, int64_t N, int H, int W,
                                                        int* __restrict__ out) {

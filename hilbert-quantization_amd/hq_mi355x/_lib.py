@@ -136,6 +136,11 @@ SIGNATURES = {
     "hq_cosqf_scores": (_i, [_p, _p, _i, _p, _p, _i64, _i, _p, _p]),
     "hq_cosqf_topk_workspace_size": (_sz, [_i, _i64, _i]),
     "hq_cosqf_topk": (_i, [_p, _p, _i, _p, _p, _i64, _i, _i, _d, _i, _i64, _p, _sz, _p, _p, _p]),
+    "hq_comp_describe": (_i, [_i, _p, _i64, _i, _i, _p, _p]),
+    "hq_comp_scores": (_i, [_i, _p, _p, _i, _p, _p, _i64, _i, _i, _p, _i, _p, _p, _p]),
+    "hq_comp_layout": (_i, [_i, _i, _i, _p]),
+    "hq_comp_padded_k": (_i, [_i, _i, _i]),
+    "hq_comp_prepare": (_i, [_p, _i64, _i64, _i, _i, _i, _i, _p, _p, _p, _p]),
 }
 
 _lock = threading.Lock()

@@ -1105,6 +1105,92 @@ def cosine_scores(a, b, exc=None):
     return cosine_scores_f64(a, b, exc)
 
 
+# ------------------------------------------------ comprehensive frame similarity (hq_comp.hip)
+
+
+def _frames3(x):
+    """Enhanced frames [N, H, W] (or one [H, W]) as a contiguous float32 / float64 device tensor."""
+    t = torch()
+    if x.dtype not in (t.float32, t.float64):
+        x = x.to(t.float64)
+    if x.dim() == 2:
+        x = x.unsqueeze(0)
+    if x.dim() != 3:
+        raise ValueError("enhanced frames must be [N, H, W]")
+    return _contig(x)
+
+
+def comp_describe(frames, exc=None):
+    """Per enhanced frame (h, L, width, row_mask) -> device int32 [N, 4] (hq_comp_describe): the detected original
+    height, the number of non-zero index rows below it, their largest trimmed length, their bit set."""
+    t = torch()
+    x = _frames3(frames)
+    N, H, W = (int(d) for d in x.shape)
+    desc = t.empty((N, 4), dtype=t.int32, device=x.device)
+    if N:
+        _chk(_L().hq_comp_describe(dtype_code(x.dtype), ptr(x), N, H, W, ptr(desc), stream()), exc)
+    return desc
+
+
+def comp_scores(q, desc_q, c, desc_c, weights, parts: bool = False, exc=None):
+    """The exact comprehensive score of every query frame [Q, H, W] against every frame [N, H, W] (one dtype,
+    float32 or float64) from their comp_describe descriptors -> device f64 [Q, N] (and the components [Q, N, 3]
+    with parts=True).  weights: host float64 [M + 1, M], row m = calculate_granularity_weights(m), M >= every L."""
+    t = torch()
+    q3, c3 = _frames3(q), _frames3(c)
+    if q3.dtype != c3.dtype or q3.shape[1:] != c3.shape[1:]:
+        raise ValueError(f"frames differ: {tuple(q3.shape[1:])} {q3.dtype} vs {tuple(c3.shape[1:])} {c3.dtype}")
+    Q, H, W = (int(d) for d in q3.shape)
+    N = int(c3.shape[0])
+    wt = np.ascontiguousarray(weights, dtype=np.float64)
+    ML = int(wt.shape[1]) if wt.ndim == 2 and wt.shape[0] > 1 else 0
+    wd = t.as_tensor(wt.reshape(-1) if ML else np.zeros(1), device=q3.device)
+    out = t.empty((Q, N), dtype=t.float64, device=q3.device)
+    pt = t.empty((Q, N, 3), dtype=t.float64, device=q3.device) if parts else None
+    if Q and N:
+        _chk(_L().hq_comp_scores(dtype_code(q3.dtype), ptr(q3), ptr(_contig(desc_q)), Q, ptr(c3), ptr(_contig(desc_c)),
+                                 N, H, W, ptr(wd), ML, ptr(out), ptr(pt) if parts else None, stream()), exc)
+    return (out, pt) if parts else out
+
+
+COMP_LAYOUT_FIELDS = ("K", "L", "ws", "stride", "ni", "nj", "off_win", "off_orig", "off_levels", "off_const",
+                      "off_orig_ind", "off_win_ind")
+
+
+def comp_layout(H: int, W: int, h: int, exc=None) -> dict:
+    """The composite row of profile (h, L = H - h) of H x W frames (hq_comp_layout): its length K, the window
+    geometry and the section offsets."""
+    buf = (ctypes.c_int32 * 12)()
+    k = _L().hq_comp_layout(int(H), int(W), int(h), buf)
+    if k < 0:
+        _chk(k, exc)
+    return dict(zip(COMP_LAYOUT_FIELDS, (int(v) for v in buf)))
+
+
+def comp_prepare(frames, h: int, side: int, level_coef, exc=None) -> CosRows:
+    """Float32 enhanced frames [N, H, W] of profile (h, L = H - h, every index row non-zero; the caller has
+    checked the descriptors) -> their composite rows as a cosine operand (hq_comp_prepare): cosine_scores_mfma and
+    cosine_topk of a side-0 (query) against a side-1 (corpus) operand return the comprehensive score.
+    level_coef: host float64 [H - h], sqrt(0.5 w_l / sum w)."""
+    t = torch()
+    x = _frames3(frames)
+    if x.dtype != t.float32:
+        raise TypeError("comp_prepare expects float32 frames")
+    N, H, W = (int(d) for d in x.shape)
+    K = comp_layout(H, W, h, exc)["K"]
+    lc = np.ascontiguousarray(level_coef, dtype=np.float64).reshape(-1)
+    if lc.size != H - int(h):
+        raise ValueError(f"{lc.size} level coefficients for {H - int(h)} index rows")
+    lcd = t.as_tensor(lc if lc.size else np.zeros(1), device=x.device)
+    Kp = int(_L().hq_cos_padded_k(K))
+    Np = int(_L().hq_cos_padded_rows(N))
+    X16 = t.empty((max(Np, 1), 2, Kp), dtype=t.float16, device=x.device)
+    inv = t.empty(max(Np, 1), dtype=t.float64, device=x.device)
+    if N:
+        _chk(_L().hq_comp_prepare(ptr(x), N, H * W, H, W, int(h), int(side), ptr(lcd), ptr(X16), ptr(inv), stream()), exc)
+    return CosRows(X16, inv, N, K)
+
+
 # ------------------------------------------------ compressed-domain frame search (u8 frames, exact)
 
 

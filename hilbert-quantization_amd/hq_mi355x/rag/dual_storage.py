@@ -141,12 +141,16 @@ class DualStorageCorpus:
         "spatial" = _calculate_spatial_locality_similarity (engine.py:662-714); "embedding" =
         _calculate_embedding_cosine_similarity of the extracted original embeddings (engine.py:604-660;
         a pair whose original heights differ compares flattened prefixes of different shapes, which the
-        reference truncates to the shorter: such pairs are scored on their common flattened prefix)."""
+        reference truncates to the shorter: such pairs are scored on their common flattened prefix);
+        "comprehensive" = _calculate_comprehensive_similarity (engine.py:516-575), the score the reference's
+        calculate_embedding_similarity ranks with (similarity.comprehensive_scores)."""
         t = torch()
         q = to_dev(query_frames)
         q = (q.unsqueeze(0) if q.dim() == 2 else q).to(self.frames.dtype)
         if method == "spatial":
             return S.spatial_locality_scores(q, self.frames)
+        if method == "comprehensive":
+            return S.comprehensive_scores(q, self.frames)
         if method != "embedding":
             raise ValueError(f"unknown method {method!r}")
         qo, qh = self._originals(q)

@@ -535,3 +535,223 @@ def apply_progressive_threshold(candidate_scores: Sequence[Tuple[int, float]], l
     out, cnt = progressive_threshold_batch(sc[None], level, ids[None])
     n = int(to_np(cnt)[0])
     return [int(x) for x in to_np(out)[0][:n]]
+
+
+# ------------------------------------------------------------------ comprehensive similarity (:478-727)
+
+_WIDTH_ERROR = "Query and candidate indices must have the same shape"
+
+
+def similarity_weights() -> dict:
+    """engine.py:716-727."""
+    return {"hierarchical": 0.5, "embedding": 0.3, "spatial": 0.2}
+
+
+def _weight_table(max_levels: int) -> np.ndarray:
+    """Row m = calculate_granularity_weights(m), zero padded: float64 [max_levels + 1, max_levels]."""
+    tab = np.zeros((max_levels + 1, max(max_levels, 1)), dtype=np.float64)
+    for m in range(1, max_levels + 1):
+        tab[m, :m] = calculate_granularity_weights(m)
+    return tab
+
+
+def _level_coef(levels: int) -> np.ndarray:
+    """sqrt(2 a_l), a_l = 0.5 (w_l / sum w) / 2, the sum taken left to right as _compare_multi_level_indices does."""
+    w = calculate_granularity_weights(levels)
+    tw = 0.0
+    for l in range(levels):
+        tw += w[l]
+    return np.sqrt(0.5 * w / tw) if levels else np.zeros(0)
+
+
+def _comp_frames(x, dtype=None):
+    """Enhanced frames [N, H, W] (or one [H, W]) on the device, float32 or float64 (`dtype` when given)."""
+    t = torch()
+    f = to_dev(x)
+    if f.dim() == 2:
+        f = f.unsqueeze(0)
+    if f.dim() != 3:
+        raise ValueError("enhanced frames must be [N, H, W] or [H, W]")
+    if dtype is not None:
+        return f.to(dtype).contiguous()
+    return (f if f.dtype in (t.float32, t.float64) else f.to(t.float64)).contiguous()
+
+
+def _check_widths(dq: np.ndarray, dc: np.ndarray):
+    """The reference pads each frame's index rows to its own largest trimmed length and raises when a pair with
+    index rows on both sides differs in it (engine.py:1013-1014): checked on the host before the scoring launch."""
+    wq = set(dq[dq[:, 1] >= 1, 2].tolist())
+    wc = set(dc[dc[:, 1] >= 1, 2].tolist())
+    if wq and wc and len(wq | wc) > 1:
+        raise ValueError(_WIDTH_ERROR)
+
+
+def _comp_exact(q3, dq_dev, dq, c3, dc_dev, dc, parts: bool = False):
+    _check_widths(dq, dc)
+    ml = int(max(dq[:, 1].max(initial=0), dc[:, 1].max(initial=0)))
+    return K.comp_scores(q3, dq_dev, c3, dc_dev, _weight_table(ml), parts)
+
+
+def comprehensive_scores(queries, frames, parts: bool = False):
+    """_calculate_comprehensive_similarity (engine.py:516-575) of every query frame [Q, H, W] against every stored
+    enhanced frame [N, H, W] -> device f64 [Q, N]; parts=True adds the components [Q, N, 3] (hierarchical,
+    embedding, spatial).  The exact route (hq_comp_describe + hq_comp_scores): float64 frames in float64, float32
+    frames from their float32 values.  ValueError with the reference's message when a pair whose frames both have
+    index rows differs in index width."""
+    t = torch()
+    q3, c3 = _comp_frames(queries), _comp_frames(frames)
+    if q3.dtype != c3.dtype:
+        q3, c3 = q3.to(t.float64), c3.to(t.float64)
+    if q3.shape[1:] != c3.shape[1:]:
+        raise ValueError(f"frame shapes differ: {tuple(q3.shape[1:])} vs {tuple(c3.shape[1:])}")
+    dq_dev, dc_dev = K.comp_describe(q3), K.comp_describe(c3)
+    return _comp_exact(q3, dq_dev, to_np(dq_dev), c3, dc_dev, to_np(dc_dev), parts)
+
+
+def calculate_comprehensive_similarity(query, query_indices, candidate_frame, frame_number=None) -> float:
+    """Drop-in for engine.py:516-575 on two enhanced frames; query_indices and frame_number are accepted and
+    ignored (the index rows are read from the query frame itself, as the reference's caller extracts them)."""
+    a, b = np.asarray(query), np.asarray(candidate_frame)
+    if a.ndim != 2 or a.shape != b.shape or a.size == 0:
+        raise ValueError("calculate_comprehensive_similarity expects two enhanced frames of one shape [H, W]")
+    return float(to_np(comprehensive_scores(a, b))[0, 0])
+
+
+def calculate_embedding_similarity(query_embedding, cached_frames: dict) -> List[Tuple[int, float]]:
+    """Drop-in for engine.py:478-514: [(frame_number, score), ...] over the cached frames, stable-sorted by score
+    descending (ties keep the dict's order) — one batched launch instead of a Python loop per frame."""
+    q = np.asarray(query_embedding)
+    if q.size == 0 or not cached_frames:
+        return []
+    keys = list(cached_frames.keys())
+    stack = np.stack([np.asarray(cached_frames[k]) for k in keys])
+    sc = comprehensive_scores(q, stack)
+    s, ids, _, _ = K.select_topk(sc, len(keys))  # (score desc, position asc) = the reference's stable sort
+    s, ids = to_np(s)[0], to_np(ids)[0]
+    return [(keys[int(i)], float(v)) for v, i in zip(s, ids)]
+
+
+class ComprehensiveFrameCorpus:
+    """Enhanced frames [N, H, W] kept resident for the RAG engine's comprehensive ranking
+    (calculate_embedding_similarity, engine.py:478-575).
+
+    The store is described once (hq_comp_describe).  A float32 store written by one generator — every frame the
+    same detected height h < H, every index row non-zero, one index width — is `fused`: its frames become
+    "composite" rows (hq_comp_prepare: level-normalised index rows, normalised original block and windows, validity
+    indicators, one constant column) whose dot product with a query's composite row is an affine
+    function of the comprehensive score, and only that operand stays resident (`K` halves x 2 per frame,
+    `resident_bytes`; about 82 KB for a 67 x 64 frame against 17 KB raw — the price of a search that is one matrix
+    core contraction with the top-k in its epilogue).  keep_frames=True keeps the raw frames as well, so that
+    queries off the profile (another height, a dropped index row) can take the exact route; without them such a
+    query raises ValueError.  Any other store keeps the frames and their descriptors and is searched by the exact
+    route (hq_comp_scores + hq_select_topk).
+
+    Fused scores are within 1e-5 of the exact ones (profiles/comp_error_bounds.txt has the measured error) and
+    the lists equal select_topk of the fused dense scores bit for bit.  Appending, replacing and removing frames
+    are out of scope: build a new corpus."""
+
+    def __init__(self, frames, keep_frames: bool = False):
+        t = torch()
+        x = _comp_frames(frames)
+        self.N, self.H, self.W = (int(d) for d in x.shape)
+        self.dtype = x.dtype
+        self._desc_dev = K.comp_describe(x)
+        self._desc = to_np(self._desc_dev)
+        self.profile = None
+        self._rows = None
+        d = self._desc
+        if self.N and x.dtype == t.float32:
+            h, L, width = int(d[0, 0]), int(d[0, 1]), int(d[0, 2])
+            if h < self.H and L == self.H - h and bool((d == d[0]).all()):
+                self.profile = (h, L, width)
+                self._coef = _level_coef(L)
+                self._rows = K.comp_prepare(x, h, 1, self._coef)
+        self._frames = x if (self._rows is None or keep_frames) else None
+        if self._frames is None:
+            self._desc_dev = None
+
+    @property
+    def fused(self) -> bool:
+        return self._rows is not None
+
+    @property
+    def K(self):
+        """Composite row length (None for a store that is not fused)."""
+        return self._rows.K if self._rows is not None else None
+
+    def __len__(self) -> int:
+        return self.N
+
+    @property
+    def resident_bytes(self) -> int:
+        n = 0
+        if self._rows is not None:
+            n += self._rows.X16.numel() * 2 + self._rows.inv.numel() * 8
+        if self._frames is not None:
+            n += self._frames.numel() * self._frames.element_size() + self.N * 16
+        return n
+
+    def _route(self, queries):
+        """(query frames, their descriptors on the device and the host, bool [Q]: on the fused profile)."""
+        q3 = _comp_frames(queries)
+        if tuple(q3.shape[1:]) != (self.H, self.W):
+            raise ValueError(f"query frames {tuple(q3.shape[1:])} are not [{self.H}, {self.W}]")
+        if q3.dtype != self.dtype:
+            q3 = q3.to(self.dtype)
+        dq_dev = K.comp_describe(q3)
+        dq = to_np(dq_dev)
+        on = np.zeros(len(dq), dtype=bool)
+        if self.fused:
+            h, L, width = self.profile
+            on = (dq[:, 0] == h) & (dq[:, 1] == L) & (dq[:, 2] == width)
+        if not on.all() and self._frames is None:
+            raise ValueError("a query is off the fused profile and the corpus was built without keep_frames=True")
+        return q3, dq_dev, dq, on
+
+    def _split(self, queries, fused_fn, exact_fn, empty):
+        """Each query through its own route, results back in query order."""
+        t = torch()
+        q3, dq_dev, dq, on = self._route(queries)
+        if on.all() and len(on):
+            return fused_fn(K.comp_prepare(q3, self.profile[0], 0, self._coef))
+        if not on.any():
+            return exact_fn(q3, dq_dev, dq)
+        out = empty(len(on), q3.device)
+        i_on = t.as_tensor(np.flatnonzero(on), device=q3.device)
+        i_off = t.as_tensor(np.flatnonzero(~on), device=q3.device)
+        got_on = fused_fn(K.comp_prepare(q3[i_on], self.profile[0], 0, self._coef))
+        got_off = exact_fn(q3[i_off].contiguous(), dq_dev[i_off].contiguous(), dq[~on])
+        for o, a, b in zip(out, got_on, got_off):
+            o[i_on], o[i_off] = a, b
+        return out
+
+    def scores(self, queries):
+        """The dense comprehensive scores [Q, N] (device f64): composite operands on the matrix cores for queries on
+        a fused store's profile, hq_comp_scores for the others."""
+        t = torch()
+        return self._split(
+            queries,
+            lambda rows: (K.cosine_scores_mfma(rows, self._rows),),
+            lambda q3, dq_dev, dq: (_comp_exact(q3, dq_dev, dq, self._frames, self._desc_dev, self._desc),),
+            lambda Q, dev: (t.empty((Q, self.N), dtype=t.float64, device=dev),))[0]
+
+    def search(self, queries, k: int = 10, threshold=None):
+        """queries [Q, H, W] (or one frame) -> device (scores [Q, k] f64, ids [Q, k] i64), (score desc, frame asc),
+        -inf / -1 where fewer than k frames pass `threshold` (None: no test; else score >= threshold).  Queries on
+        the profile of a fused store: hq_comp_prepare + hq_cos_topk (k > 64: the dense fused scores and
+        hq_select_topk); the others: hq_comp_scores + hq_select_topk."""
+        t = torch()
+        k = int(k)
+        if k < 1:
+            raise ValueError(f"k = {k}")
+        thr, mode = _threshold_mode(threshold)
+
+        def exact(q3, dq_dev, dq):
+            s, ids, _, _ = K.select_topk(_comp_exact(q3, dq_dev, dq, self._frames, self._desc_dev, self._desc), k, thr,
+                                         mode)
+            return s, ids
+
+        return self._split(
+            queries, lambda rows: K.cosine_topk(rows, self._rows, k, thr, mode), exact,
+            lambda Q, dev: (t.full((Q, k), float("-inf"), dtype=t.float64, device=dev),
+                            t.full((Q, k), -1, dtype=t.int64, device=dev)))

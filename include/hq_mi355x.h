@@ -756,6 +756,44 @@ int hq_spatial_locality(int dtype, const void* q, int Q, const void* c, int64_t 
 int hq_threshold_select(const double* scores, const int64_t* ids, int Q, int64_t N, double threshold, int64_t cap,
                         int64_t* out_ids, int64_t* out_count, hq_stream_t stream);
 
+/* ---- S7: the comprehensive frame similarity (rag/search/engine.py:478-727, hq_comp.hip) -----------
+ * score = 0.5 hierarchical + 0.3 embedding + 0.2 spatial of two enhanced frames [H, W] (float32 or float64):
+ * hierarchical = compare_hierarchical_indices of the frames' non-zero index rows (the rows below the detected
+ * height, all-zero rows dropped, zero-padded to M = max(L_q, L_c) levels, weights of M levels; 0.0 when a frame
+ * has none), embedding = the cosine of the original blocks (flattened, truncated to the common length), spatial =
+ * hq_spatial_locality's windowed cosine.
+ * hq_comp_describe: per frame desc[4 i ..] = (h, L, width, row_mask): detected height, number of non-zero rows
+ *   among h .. H - 1, their largest length without trailing zeros, their bit set (bit r - h).  One launch.  A
+ *   frame with more than 31 rows below its height: HQ_E_UNSUPPORTED (its L is written as -1; for H > 32 the call
+ *   reads one flag back and synchronises the stream).
+ * hq_comp_scores: out [Q, N] f64 = the score of every pair from the frames and their descriptors (heights are
+ *   not detected again); parts [Q, N, 3] (or NULL) = the three components.  weights: the host table of
+ *   calculate_granularity_weights, (max_levels + 1) rows of max_levels, row M = the weights of M levels; every
+ *   max(L_q, L_c) must be <= max_levels (a pair above it gets a NaN hierarchical part).  The caller checks that
+ *   pairs with L_q, L_c >= 1 share `width` (the reference raises ValueError otherwise).  One wave per pair, the
+ *   query frame staged in LDS: (5 max_windows + H W) values must fit 160 KiB.  |err| < 1e-12 for float64 frames,
+ *   < 1e-6 against the reference's float32 arithmetic.
+ * hq_comp_layout: the composite row of profile (h, L = H - h): returns its length K (< 0: error) and, when out
+ *   is not NULL, out[12] = (K, L, ws (0 when < 2), stride, windows down, windows across, and the offsets of the
+ *   sections in row order: the windows, the original block, the levels, the constant column, the block's
+ *   indicator, the windows' indicators).  hq_comp_padded_k = K rounded up as hq_cos_padded_k rounds.
+ * hq_comp_prepare: float32 frames imgs [N, H, W] (frame stride ld) of that profile (the caller has checked
+ *   desc == (h, H - h, ., full mask)) -> composite rows in hq_cos_prepare's tiled layout: X16 of
+ *   hq_cos_padded_rows(N) x 2 x hq_comp_padded_k halves and inv [hq_cos_padded_rows(N)].  level_coef[l] =
+ *   sqrt(0.5 w_l / sum w) for the H - h levels; side 0 = queries, 1 = corpus (the constant column).  Rows are
+ *   stored unscaled (every entry is at most 1), inv = 1 (0 for a pad row and for a frame holding a NaN or inf: it
+ *   scores 0.0), so
+ *   hq_cos_scores_mfma / _f32 / hq_cos_topk on two such operands return the comprehensive score (within 1e-5;
+ *   profiles/comp_error_bounds.txt has the measured error).                                              */
+int hq_comp_describe(int dtype, const void* imgs, int64_t N, int H, int W, int32_t* desc, hq_stream_t stream);
+int hq_comp_scores(int dtype, const void* q, const int32_t* desc_q, int Q, const void* c, const int32_t* desc_c,
+                   int64_t N, int H, int W, const double* weights, int max_levels, double* out, double* parts,
+                   hq_stream_t stream);
+int hq_comp_layout(int H, int W, int h, int32_t* out);
+int hq_comp_padded_k(int H, int W, int h);
+int hq_comp_prepare(const float* imgs, int64_t N, int64_t ld, int H, int W, int h, int side, const double* level_coef,
+                    void* X16, double* inv, hq_stream_t stream);
+
 /* ---- §8e: the sharded search's one collective (RCCL over xGMI) ----------------------------------
  * The corpus is split into contiguous global-id ranges, one per GPU (one process per GPU); each rank
  * answers the whole query batch against its shard and packs fixed-size top-k records, and ONE
