@@ -1167,16 +1167,33 @@ def comp_layout(H: int, W: int, h: int, exc=None) -> dict:
     return dict(zip(COMP_LAYOUT_FIELDS, (int(v) for v in buf)))
 
 
+COMP_LDS_BYTES = 160 * 1024
+
+
+def comp_prepare_fits(H: int, W: int, h: int) -> bool:
+    """Whether hq_comp_prepare takes the profile: it keeps one float64 coefficient per section (H - h levels, the
+    block, every window) of a tile's 16 frames in LDS, 160 KiB at the most (include/hq_mi355x.h); beyond that it
+    returns HQ_E_UNSUPPORTED."""
+    lay = comp_layout(H, W, h)
+    return 16 * 8 * (lay["L"] + 1 + lay["ni"] * lay["nj"]) <= COMP_LDS_BYTES
+
+
 def comp_prepare(frames, h: int, side: int, level_coef, exc=None) -> CosRows:
     """Float32 enhanced frames [N, H, W] of profile (h, L = H - h, every index row non-zero; the caller has
     checked the descriptors) -> their composite rows as a cosine operand (hq_comp_prepare): cosine_scores_mfma and
     cosine_topk of a side-0 (query) against a side-1 (corpus) operand return the comprehensive score.
-    level_coef: host float64 [H - h], sqrt(0.5 w_l / sum w)."""
+    level_coef: host float64 [H - h], sqrt(0.5 w_l / sum w).  A [N, H, W] view whose frames are contiguous but lie
+    more than H W values apart (frames cut out of a wider buffer) is read in place: its stride(0) is the kernel's ld."""
     t = torch()
-    x = _frames3(frames)
+    x = frames
+    strided = (x.dim() == 3 and x.dtype == t.float32 and x.shape[0] > 1 and x.stride(2) == 1
+               and x.stride(1) == x.shape[2] and x.stride(0) > x.shape[1] * x.shape[2])
+    if not strided:
+        x = _frames3(frames)
     if x.dtype != t.float32:
         raise TypeError("comp_prepare expects float32 frames")
     N, H, W = (int(d) for d in x.shape)
+    ld = int(x.stride(0)) if strided else H * W
     K = comp_layout(H, W, h, exc)["K"]
     lc = np.ascontiguousarray(level_coef, dtype=np.float64).reshape(-1)
     if lc.size != H - int(h):
@@ -1187,7 +1204,7 @@ def comp_prepare(frames, h: int, side: int, level_coef, exc=None) -> CosRows:
     X16 = t.empty((max(Np, 1), 2, Kp), dtype=t.float16, device=x.device)
     inv = t.empty(max(Np, 1), dtype=t.float64, device=x.device)
     if N:
-        _chk(_L().hq_comp_prepare(ptr(x), N, H * W, H, W, int(h), int(side), ptr(lcd), ptr(X16), ptr(inv), stream()), exc)
+        _chk(_L().hq_comp_prepare(ptr(x), N, ld, H, W, int(h), int(side), ptr(lcd), ptr(X16), ptr(inv), stream()), exc)
     return CosRows(X16, inv, N, K)
 
 

@@ -646,6 +646,12 @@ class ComprehensiveFrameCorpus:
     query raises ValueError.  Any other store keeps the frames and their descriptors and is searched by the exact
     route (hq_comp_scores + hq_select_topk).
 
+    A profile is fused only while hq_comp_prepare can stage it: 16 frames x (L + 1 + n_windows) section coefficients
+    in 160 KiB of LDS, i.e. at most 1280 - L - 1 windows (67 x 64 frames have 961; the generator's 131 x 128 frames
+    have 3969 and are not fused).  Such a store takes the exact route, and where that cannot stage a frame either
+    (hq_comp_scores: 5 max_windows + H W values in 160 KiB, which 131 x 128 exceeds) scores() and search() raise the
+    library's HQ_E_UNSUPPORTED message; nothing is computed another way.
+
     Fused scores are within 1e-5 of the exact ones (profiles/comp_error_bounds.txt has the measured error) and
     the lists equal select_topk of the fused dense scores bit for bit.  Appending, replacing and removing frames
     are out of scope: build a new corpus."""
@@ -662,7 +668,7 @@ class ComprehensiveFrameCorpus:
         d = self._desc
         if self.N and x.dtype == t.float32:
             h, L, width = int(d[0, 0]), int(d[0, 1]), int(d[0, 2])
-            if h < self.H and L == self.H - h and bool((d == d[0]).all()):
+            if h < self.H and L == self.H - h and bool((d == d[0]).all()) and K.comp_prepare_fits(self.H, self.W, h):
                 self.profile = (h, L, width)
                 self._coef = _level_coef(L)
                 self._rows = K.comp_prepare(x, h, 1, self._coef)
@@ -712,7 +718,9 @@ class ComprehensiveFrameCorpus:
         """Each query through its own route, results back in query order."""
         t = torch()
         q3, dq_dev, dq, on = self._route(queries)
-        if on.all() and len(on):
+        if not len(on) or not self.N:  # nothing to score: the padded lists / the empty matrix, no launch
+            return empty(len(on), q3.device)
+        if on.all():
             return fused_fn(K.comp_prepare(q3, self.profile[0], 0, self._coef))
         if not on.any():
             return exact_fn(q3, dq_dev, dq)

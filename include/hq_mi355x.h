@@ -784,7 +784,11 @@ int hq_threshold_select(const double* scores, const int64_t* ids, int Q, int64_t
  *   stored unscaled (every entry is at most 1), inv = 1 (0 for a pad row and for a frame holding a NaN or inf: it
  *   scores 0.0), so
  *   hq_cos_scores_mfma / _f32 / hq_cos_topk on two such operands return the comprehensive score (within 1e-5;
- *   profiles/comp_error_bounds.txt has the measured error).                                              */
+ *   profiles/comp_error_bounds.txt has the measured error, up to K = 20,627).  A tile's 16 frames keep one float64
+ *   coefficient per section in LDS: 16 (H - h + 1 + n_windows) values must fit 160 KiB, i.e. at most
+ *   1279 - (H - h) windows (67 x 64 frames: 961).  A profile beyond that, such as the RAG generator's 131 x 128
+ *   frames (3969 windows, K = 84,243), is HQ_E_UNSUPPORTED: it cannot be fused, and since hq_comp_scores cannot
+ *   stage such a frame either, callers refuse it (ComprehensiveFrameCorpus passes the message on).           */
 int hq_comp_describe(int dtype, const void* imgs, int64_t N, int H, int W, int32_t* desc, hq_stream_t stream);
 int hq_comp_scores(int dtype, const void* q, const int32_t* desc_q, int Q, const void* c, const int32_t* desc_c,
                    int64_t N, int H, int W, const double* weights, int max_levels, double* out, double* parts,

@@ -12,7 +12,14 @@ family under the frame numbers <tag>_rank_keys).
 Edge frames e_<name>_<tag>: _enh [H, W], _desc [3], _score [2, 9] (row 0: the edge frame as the query against
 the family's 8 frames and itself, row 1: as the candidate), _parts [2, 9, 3].  Stand-alone sets s_<name>:
 _enh [n, H, W], _desc [n, 3], _score [n, n], _parts [n, n, 3].  e_width_enh [2, 9, 8] with e_width_raised = 1
-when the reference raised ValueError for the pair."""
+when the reference raised ValueError for the pair.
+
+shape_fixtures() -> tests/golden/comprehensive_shapes.npz: hand-built frames (tests/comp_sweep_cases.build_frame) at
+the shapes the first file lacks, 5 frames each (full, noisy, independent, first index row dropped, zero patch), in
+float64 (<set>) and float32 (<set>f): wide 12 x 100, odd 20 x 65, small 6 x 4 (ws < 2 with index rows), rows31
+40 x 8 (31 index rows).  Per set g_<set>_enh / _desc / _score / _parts as for the stand-alone sets.  nonfinite: 9 x 8
+frames, frame 1 with a NaN and frame 2 with an inf in the data block, frame 3 with a NaN in its index row;
+g_<set>_raised [n, n] is 1 where the reference raised for the pair (its score and parts are then recorded as NaN)."""
 import argparse
 import os
 import sys
@@ -159,6 +166,52 @@ def fixtures():
     return out
 
 
+SHAPE_SETS = (("wide", 12, 100, 10), ("odd", 20, 65, 17), ("small", 6, 4, 4), ("rows31", 40, 8, 9))
+
+
+def _matrix_recorded(obj, qs, cs):
+    """_matrix that records what the reference does with a pair instead of assuming it: raised = 1 and NaN entries
+    where it raised."""
+    sc = np.full((len(qs), len(cs)), np.nan)
+    pt = np.full((len(qs), len(cs), 3), np.nan)
+    raised = np.zeros((len(qs), len(cs)), dtype=np.int64)
+    for a, q in enumerate(qs):
+        for b, c in enumerate(cs):
+            try:
+                sc[a, b], pt[a, b] = _pair(obj, q, c)
+            except Exception:  # noqa: BLE001 - whatever it raises is the recorded behaviour
+                raised[a, b] = 1
+    return sc, pt, raised
+
+
+def shape_fixtures():
+    sys.path.insert(0, os.path.dirname(HERE))
+    import comp_sweep_cases as SW
+    obj = _engine()
+    rng = np.random.default_rng(78)
+    out = {}
+
+    def record(name, frames):
+        for tag, dt in ((name, np.float64), (name + "f", np.float32)):
+            enh = np.stack(frames).astype(dt)
+            out[f"g_{tag}_enh"] = enh
+            out[f"g_{tag}_desc"] = np.stack([_desc(obj, e) for e in enh])
+            out[f"g_{tag}_score"], out[f"g_{tag}_parts"], out[f"g_{tag}_raised"] = _matrix_recorded(obj, enh, enh)
+
+    for name, H, W, h in SHAPE_SETS:
+        base, _ = SW.build_frame(rng, H, W, h)
+        record(name, [base, SW.build_frame(rng, H, W, h, "noisy", base)[0], SW.build_frame(rng, H, W, h)[0],
+                      SW.build_frame(rng, H, W, h, "drop_first", base)[0],
+                      SW.build_frame(rng, H, W, h, "zero_patch", base)[0]])
+    base, _ = SW.build_frame(rng, 9, 8, 8)
+    nan_block, inf_block, nan_row = base.copy(), base.copy(), base.copy()
+    nan_block[3, 5] = np.nan
+    inf_block[2, 1] = np.inf
+    nan_row[8, 1] = np.nan
+    record("nonfinite", [base, nan_block, inf_block, nan_row, SW.build_frame(rng, 9, 8, 8, "noisy", base)[0]])
+    return out
+
+
 def main():
     from make_golden import _import_reference
     ap = argparse.ArgumentParser()
@@ -167,6 +220,10 @@ def main():
     _import_reference(a.ref)
     d = fixtures()
     path = os.path.join(HERE, "comprehensive.npz")
+    np.savez_compressed(path, **d)
+    print(f"wrote {path}: {len(d)} arrays, {os.path.getsize(path)} bytes")
+    d = shape_fixtures()
+    path = os.path.join(HERE, "comprehensive_shapes.npz")
     np.savez_compressed(path, **d)
     print(f"wrote {path}: {len(d)} arrays, {os.path.getsize(path)} bytes")
 

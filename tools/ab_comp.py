@@ -14,7 +14,10 @@ queries; --unfused-q queries x --unfused-n frames) and their times are scaled to
 says so next to every scaled number.  Every variant runs between two HIP events after a warm-up call.
 
 errors (--what errors, written to profiles/comp_error_bounds.txt): the largest and the mean |fused - exact| per
-row family (gaussian, same-sign, near-duplicate, negated: queries that are the negation of a stored frame) and shape.
+row family (gaussian, same-sign, near-duplicate, negated: queries that are the negation of a stored frame) and shape:
+the RAG generator's four square profiles, then hand-built profiles (H, W, h) that reach the other window geometries
+(ws < 2 with index rows, ws 3 at stride 1, odd and wide W, 31 index rows), and a line for the generator's 131 x 128
+frames, which hq_comp_prepare does not take.
 
 usage: ab_comp.py --what timing|errors [--out FILE] [--queries 1000] [--reps 3]
 Needs an MI355X."""
@@ -47,6 +50,9 @@ OUT = args.out or os.path.join(ROOT, "profiles", "comp_vs_unfused.txt" if args.w
 LINES = []
 GRAN = {8: (2,), 16: (4, 2), 32: (4, 2), 64: (8, 4, 2)}   # the RAG generator's index rows, finest first
 HEIGHT = {8: 8, 16: 17, 32: 32, 64: 65}                  # detected height of an enhanced n x n frame
+# (H, W, h): ws < 2 with index rows; ws 2; ws 3 (stride 1) twice; ws 4; W > 64; odd W; 945 windows; 31 index rows
+BUILT_PROFILES = ((6, 4, 4), (9, 8, 8), (13, 12, 12), (15, 16, 14), (18, 16, 17), (12, 100, 10), (20, 65, 17),
+                  (35, 128, 32), (40, 8, 9))
 
 
 def say(s=""):
@@ -54,11 +60,11 @@ def say(s=""):
     LINES.append(s)
 
 
-def enhance(img):
+def enhance(img, gran=None):
     """[M, n, n] float32 images -> [M, n + rows, n] enhanced frames (block means per granularity, one row each)."""
     M, n, _ = img.shape
     rows = []
-    for g in GRAN[n]:
+    for g in gran or GRAN[n]:
         r = torch.zeros((M, n), dtype=img.dtype, device=img.device)
         r[:, :g * g] = img.reshape(M, g, n // g, g, n // g).mean(dim=(2, 4)).reshape(M, g * g)
         rows.append(r)
@@ -166,6 +172,40 @@ def errors():
             d = (corpus.scores(qs) - S.comprehensive_scores(qs, fr)).abs()
             say(f"frames {fr.shape[1]:>2} x {n:<2} K = {corpus.K:>5}  {name:<15} max {float(d.max()):.3e}  mean "
                 f"{float(d.mean()):.3e}")
+    say("# hand-built profiles (H x W, detected height h): a gaussian block of h rows, then H - h index rows that are")
+    say("# non-zero in their first W / 2 - 1 columns and in the last one")
+    for H, W, h in BUILT_PROFILES:
+
+        def rnd(*shape):
+            return torch.randn(shape, generator=g, dtype=torch.float32, device="cuda")
+
+        def built(x):
+            x = x.clone()
+            x[:, h:, max(W // 2, 1) - 1:W - 1] = 0.0
+            return x.contiguous()
+
+        base = rnd(256, H, W)
+        fams = {
+            "gaussian": (rnd(16, H, W), base),
+            "same-sign": (rnd(16, H, W).abs() + 1.0, base.abs() + 1.0),
+            "near-duplicate": (base[:1] + 1e-3 * rnd(16, H, W), base[:1] + 1e-3 * rnd(256, H, W)),
+            "negated": (-base[:16] + 0.05 * rnd(16, H, W), base),
+        }
+        for name, (qi, ci) in fams.items():
+            qs, fr = built(qi), built(ci)
+            corpus = S.ComprehensiveFrameCorpus(fr)
+            assert corpus.fused and corpus.profile[:2] == (h, H - h), (H, W, h, corpus.profile)
+            d = (corpus.scores(qs) - S.comprehensive_scores(qs, fr)).abs()
+            say(f"frames {H:>2} x {W:<3} h = {h:<2} K = {corpus.K:>5}  {name:<15} max {float(d.max()):.3e}  mean "
+                f"{float(d.mean()):.3e}")
+    # the generator's 128 x 128 images: 131 x 128 frames, h = 128, three index rows (g = 8, 4, 2)
+    lay = K.comp_layout(131, 128, 128)
+    fr = enhance(torch.randn((16, 128, 128), generator=g, dtype=torch.float32, device="cuda"), (8, 4, 2))
+    corpus = S.ComprehensiveFrameCorpus(fr)
+    say(f"frames 131 x 128 K = {lay['K']}: not measured.  {lay['ni'] * lay['nj']} windows: hq_comp_prepare keeps 16 x "
+        f"(L + 1 + windows) float64 coefficients in LDS, {16 * 8 * (lay['L'] + 1 + lay['ni'] * lay['nj'])} B > 160 KiB "
+        f"(comp_prepare_fits = {K.comp_prepare_fits(131, 128, 128)}, corpus.fused = {corpus.fused}); hq_comp_scores "
+        f"cannot stage the frame either, so the store is refused")
 
 
 (timing if args.what == "timing" else errors)()
