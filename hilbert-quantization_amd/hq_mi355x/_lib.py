@@ -141,6 +141,9 @@ SIGNATURES = {
     "hq_comp_layout": (_i, [_i, _i, _i, _p]),
     "hq_comp_padded_k": (_i, [_i, _i, _i]),
     "hq_comp_prepare": (_i, [_p, _i64, _i64, _i, _i, _i, _i, _p, _p, _p, _p]),
+    "hq_hier_prepare": (_i, [_i, _p, _i64, _i64, _i, _i, _p, _i, _p, _p, _p]),
+    "hq_hier_workspace_size": (_sz, [_i, _i64, _i]),
+    "hq_hier_filter": (_i, [_p, _p, _p, _i, _p, _p, _i64, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p, _p]),
 }
 
 _lock = threading.Lock()

@@ -1208,6 +1208,110 @@ def comp_prepare(frames, h: int, side: int, level_coef, exc=None) -> CosRows:
     return CosRows(X16, inv, N, K)
 
 
+# ------------------------------------------------ progressive hierarchical search (hq_hier.hip)
+
+HIER_MAX_LEVELS = 8
+HIER_MAX_K = 64
+
+
+class HierRows:
+    """Index rows of enhanced frames as hq_hier_prepare packs them: rows [N, max_levels, W] f64 (compacted, trimmed,
+    zero padded), lens [N, max_levels] i32 (0: no such level), L [N] i32 on the device and levels (host int64 [N]):
+    every frame's level count (a frame with more than max_levels levels keeps its first max_levels rows)."""
+
+    __slots__ = ("rows", "lens", "L", "levels", "N", "W", "max_levels")
+
+    def __init__(self, rows, lens, L, levels, N, W, max_levels):
+        self.rows, self.lens, self.L, self.levels = rows, lens, L, levels
+        self.N, self.W, self.max_levels = int(N), int(W), int(max_levels)
+
+    @property
+    def nbytes(self) -> int:
+        return sum(x.numel() * x.element_size() for x in (self.rows, self.lens, self.L))
+
+
+def hier_prepare(frames, desc=None, max_levels: Optional[int] = None, clamp: bool = False, exc=None) -> HierRows:
+    """Enhanced frames [N, H, W] (float32 / float64) -> HierRows (hq_hier_prepare, one launch).  desc: their
+    comp_describe descriptors (computed when None).  max_levels: levels kept per frame (default: the largest level
+    count of the batch, at least 1).  A frame with more levels is refused with the library's HQ_E_UNSUPPORTED
+    message, unless clamp=True: then its first max_levels rows are packed and `levels` keeps the true count (the
+    query side of hier_filter)."""
+    t = torch()
+    x = _frames3(frames)
+    N, H, W = (int(d) for d in x.shape)
+    d_dev = comp_describe(x, exc) if desc is None else _contig(desc)
+    d = d_dev.cpu().numpy().astype(np.int64).reshape(N, 4)
+    levels = np.maximum(d[:, 1], 0)
+    ml = int(max_levels) if max_levels is not None else max(1, min(int(levels.max(initial=0)), HIER_MAX_LEVELS))
+    if clamp and N and int(levels.max(initial=0)) > ml:
+        d2 = d.copy()
+        for i in np.flatnonzero(levels > ml):
+            m, kept = int(d2[i, 3]) & 0xFFFFFFFF, 0
+            for _ in range(ml):  # the lowest max_levels bits of the row mask
+                low = m & -m
+                kept |= low
+                m ^= low
+            d2[i, 3], d2[i, 1] = kept, ml
+        d_dev = t.as_tensor(d2.astype(np.int32), device=x.device)
+    rows = t.empty((N, ml, W), dtype=t.float64, device=x.device)
+    lens = t.empty((N, ml), dtype=t.int32, device=x.device)
+    if N:
+        _chk(_L().hq_hier_prepare(dtype_code(x.dtype), ptr(x), N, H * W, H, W, ptr(d_dev), ml, ptr(rows), ptr(lens),
+                                  stream()), exc)
+    L = t.as_tensor(levels.astype(np.int32), device=x.device)
+    return HierRows(rows, lens, L, levels, N, W, ml)
+
+
+def hier_filter(q: HierRows, c: HierRows, thr, ratio, kout: int = 20, want_alive: bool = False,
+                workspace_bytes: int = 1 << 30, want_scores: bool = False, exc=None):
+    """The progressive hierarchical cascade of every prepared query against the prepared corpus (hq_hier_filter)
+    -> device (counts [Q, max_levels] i64, top_ids [Q, kout] i64 (-1 padded), top_scores [Q, kout, max_levels] f64,
+    alive [Q, N] u8 or None).  thr, ratio: the level tables (max_levels values each, host).  The workspace holds
+    max_levels * Qb * N float64 scores; the queries run in blocks of Qb so that it stays under workspace_bytes.
+    want_scores=True (a batch that runs as one block) appends the level scores S [max_levels, Q, N] f64: a view of
+    the calling thread's workspace, valid until its next workspace-using call on this stream."""
+    t = torch()
+    if q.W != c.W or q.max_levels != c.max_levels:
+        raise ValueError(f"query rows [{q.max_levels}, {q.W}] against corpus rows [{c.max_levels}, {c.W}]")
+    kout = int(kout)
+    if not 0 <= kout <= HIER_MAX_K:
+        raise ValueError(f"kout = {kout} (0 .. {HIER_MAX_K})")
+    ml, Q, N = c.max_levels, q.N, c.N
+    th = np.ascontiguousarray(thr, dtype=np.float64).reshape(-1)
+    ra = np.ascontiguousarray(ratio, dtype=np.float64).reshape(-1)
+    if th.size < ml or ra.size < ml:
+        raise ValueError(f"{th.size} thresholds and {ra.size} ratios for {ml} levels")
+    dev = c.rows.device
+    counts = t.zeros((Q, ml), dtype=t.int64, device=dev)
+    ids = t.full((Q, kout), -1, dtype=t.int64, device=dev)
+    sc = t.zeros((Q, kout, ml), dtype=t.float64, device=dev)
+    alive = t.zeros((Q, N), dtype=t.uint8, device=dev) if want_alive else None
+    if Q == 0 or N == 0:
+        if want_scores:
+            return counts, ids, sc, alive, t.zeros((ml, Q, N), dtype=t.float64, device=dev)
+        return counts, ids, sc, alive
+    size = _L().hq_hier_workspace_size
+    per = Q
+    limit = max(int(workspace_bytes), 1)
+    if int(size(Q, N, ml)) > limit:
+        per = max(1, limit // max(int(size(1, N, ml)), 1))
+    if want_scores and per < Q:
+        raise ValueError("want_scores=True needs the batch in one workspace block")
+    th_p = th.ctypes.data_as(ctypes.c_void_p)
+    ra_p = ra.ctypes.data_as(ctypes.c_void_p)
+    for q0 in range(0, Q, per):
+        q1 = min(Q, q0 + per)
+        wb = int(size(q1 - q0, N, ml))
+        ws = _workspace(wb, dev)
+        _chk(_L().hq_hier_filter(ptr(q.rows[q0:q1]), ptr(q.lens[q0:q1]), ptr(q.L[q0:q1]), q1 - q0, ptr(c.rows),
+                                 ptr(c.lens), N, c.W, ml, th_p, ra_p, kout, ptr(ws), ptr(counts[q0:q1]),
+                                 ptr(ids[q0:q1]) if kout else None, ptr(sc[q0:q1]) if kout else None,
+                                 ptr(alive[q0:q1]) if want_alive else None, stream()), exc)
+    if want_scores:
+        return counts, ids, sc, alive, ws[:ml * Q * N * 8].view(t.float64).view(ml, Q, N)
+    return counts, ids, sc, alive
+
+
 # ------------------------------------------------ compressed-domain frame search (u8 frames, exact)
 
 

@@ -119,6 +119,7 @@ class DualStorageCorpus:
         self.frames = x if x.dtype in (t.float32, t.float64) else x.to(t.float64)
         self.metadata = list(metadata)
         self._cos = None
+        self._hier = None
 
     @classmethod
     def from_storage(cls, storage_root: str, frames) -> "DualStorageCorpus":
@@ -168,7 +169,17 @@ class DualStorageCorpus:
         return out
 
     def search(self, query_frames, k: int = 10, method: str = "spatial") -> List[List[Tuple[VideoFrameMetadata, float]]]:
-        """Top-k stored frames per query by (score desc, frame order asc)."""
+        """Top-k stored frames per query by (score desc, frame order asc).  method="progressive": the engine's
+        workflow instead (HierarchicalFrameCorpus.search: the progressive hierarchical cascade, then the
+        comprehensive score of its first 2 k candidates, score >= 0.1, ties in the cascade's order); the store's
+        packed index rows are prepared on the first such call and stay resident."""
+        if method == "progressive":
+            if self._hier is None:
+                self._hier = S.HierarchicalFrameCorpus(self.frames)
+            q = to_dev(query_frames)
+            s, ids = self._hier.search(q.to(self.frames.dtype), int(k))
+            s, ids = to_np(s), to_np(ids)
+            return [[(self.metadata[int(i)], float(v)) for v, i in zip(s[r], ids[r]) if i >= 0] for r in range(len(s))]
         sc = self.scores(query_frames, method)
         s, ids, _, _ = K.select_topk(sc, max(1, min(int(k), len(self))), 0.0, 0)
         s, ids = to_np(s), to_np(ids)

@@ -500,13 +500,19 @@ def calculate_spatial_locality_similarity(embedding1, embedding2) -> float:
 # ------------------------------------------------------------------ progressive threshold (:243-287)
 
 
-def progressive_threshold(level: int, n_candidates: int) -> Tuple[float, int]:
-    """The level's score threshold and candidate cap, with the reference's Python float arithmetic."""
+def progressive_level(level: int) -> Tuple[float, float]:
+    """The level's score threshold and kept share, with the reference's Python float arithmetic."""
     base_threshold = 0.3
     level_factor = 0.1
     threshold = base_threshold + (level_factor * (3 - min(level, 3)))
     threshold = min(threshold, 0.8)
     ratio = 0.3 if level == 0 else (0.5 if level == 1 else 0.7)
+    return threshold, ratio
+
+
+def progressive_threshold(level: int, n_candidates: int) -> Tuple[float, int]:
+    """The level's score threshold and candidate cap, with the reference's Python float arithmetic."""
+    threshold, ratio = progressive_level(level)
     return threshold, max(1, int(n_candidates * ratio))
 
 
@@ -763,3 +769,135 @@ class ComprehensiveFrameCorpus:
             queries, lambda rows: K.cosine_topk(rows, self._rows, k, thr, mode), exact,
             lambda Q, dev: (t.full((Q, k), float("-inf"), dtype=t.float64, device=dev),
                             t.full((Q, k), -1, dtype=t.int64, device=dev)))
+
+
+# ------------------------------------------------------------------ progressive hierarchical search (:51-95)
+
+
+class HierarchicalFrameCorpus:
+    """Enhanced frames [N, H, W] (float32 or float64) prepared once for the engine's progressive hierarchical
+    search (progressive_hierarchical_search, engine.py:51-95, 178-287): the candidate cascade that runs before the
+    comprehensive score.  The store is described (hq_comp_describe) and its index rows are packed (hq_hier_prepare:
+    compacted, trimmed, float64) and kept resident, max_levels x W x 8 bytes per frame plus the lengths
+    (`resident_bytes`); keep_frames=True (the default) keeps the raw frames too, which search() needs for the
+    comprehensive re-rank.
+
+    The cascade: level l orders the survivors by (s_l desc, s_{l-1} desc, ..., s_0 desc, id asc) and
+    keeps the first max(1, int(n_prev ratio_l)) of those with s_l >= thr_l (progressive_threshold's tables).  It runs
+    on the device for a whole query batch, no host round trip between levels (hq_hier_filter).  A store with a frame
+    of more than 8 levels is refused with the library's message.  Appending and removing frames, u8 stores and
+    sharding are out of scope: build a new corpus."""
+
+    def __init__(self, frames, keep_frames: bool = True):
+        x = _comp_frames(frames)
+        self.N, self.H, self.W = (int(d) for d in x.shape)
+        self.dtype = x.dtype
+        desc_dev = K.comp_describe(x)
+        self._rows = K.hier_prepare(x, desc_dev)
+        self.max_levels = self._rows.max_levels
+        lv = [progressive_level(l) for l in range(self.max_levels)]
+        self._thr = np.array([v[0] for v in lv], dtype=np.float64)
+        self._ratio = np.array([v[1] for v in lv], dtype=np.float64)
+        self._frames = x if keep_frames else None
+        self._desc_dev = desc_dev if keep_frames else None
+        self._desc = to_np(desc_dev) if keep_frames else None
+
+    def __len__(self) -> int:
+        return self.N
+
+    @property
+    def resident_bytes(self) -> int:
+        n = self._rows.nbytes
+        if self._frames is not None:
+            n += self._frames.numel() * self._frames.element_size() + self.N * 16
+        return n
+
+    def _queries(self, queries):
+        """(query frames [Q, H, W], their descriptors on the device, their packed rows at the corpus's max_levels)."""
+        q3 = _comp_frames(queries)
+        if tuple(q3.shape[1:]) != (self.H, self.W):
+            raise ValueError(f"query frames {tuple(q3.shape[1:])} are not [{self.H}, {self.W}]")
+        dq_dev = K.comp_describe(q3)
+        return q3, dq_dev, K.hier_prepare(q3, dq_dev, self.max_levels, clamp=True)
+
+    def filter(self, queries, kout: int = 20, workspace_bytes: int = 1 << 30):
+        """queries [Q, H, W] (or one frame) -> device (top_ids [Q, kout] i64, -1 padded: the first kout candidates of
+        every query in the cascade's order; top_scores [Q, kout, max_levels] f64: their level scores; counts
+        [Q, max_levels] i64: the survivors after each level, 0 for the levels a query does not have or never
+        reached).  kout <= 64.  The level scores of a query block live in a workspace of max_levels * Qb * N * 8
+        bytes; the batch is split so that it stays under workspace_bytes."""
+        _, _, qr = self._queries(queries)
+        counts, ids, sc, _ = K.hier_filter(qr, self._rows, self._thr, self._ratio, kout, False, workspace_bytes)
+        return ids, sc, counts
+
+    def _candidates(self, qr, a: int) -> np.ndarray:
+        """The whole ordered candidate list of prepared query a (host int64): the alive mask and the level scores of
+        the survivors from the device, then one lexsort over the survivors only."""
+        t = torch()
+        one = K.HierRows(qr.rows[a:a + 1], qr.lens[a:a + 1], qr.L[a:a + 1], qr.levels[a:a + 1], 1, qr.W, qr.max_levels)
+        Lq = int(qr.levels[a])
+        if Lq == 0 or Lq > self.max_levels or self.N == 0:
+            return np.zeros(0, dtype=np.int64)
+        _, _, _, alive, S = K.hier_filter(one, self._rows, self._thr, self._ratio, 0, True, want_scores=True)
+        idx = t.nonzero(alive[0] == Lq).view(-1)
+        ids, s = to_np(idx), to_np(S[:Lq, 0][:, idx])
+        # np.lexsort: the last key is the primary one
+        return ids[np.lexsort((ids,) + tuple(-s[l] for l in range(Lq)))].astype(np.int64)
+
+    def candidates(self, query) -> List[int]:
+        """One query frame [H, W] -> the reference's progressive_hierarchical_search list (every survivor, in order)."""
+        _, _, qr = self._queries(query)
+        if qr.N != 1:
+            raise ValueError("candidates() takes one query frame [H, W]")
+        return [int(i) for i in self._candidates(qr, 0)]
+
+    def search(self, queries, k: int = 10, threshold: float = 0.1):
+        """The engine's search workflow (search_similar_documents_with_caching, engine.py:754-781, steps 2, 4, 5) for
+        queries [Q, H, W] (or one frame): the first 2 k candidates of the cascade, their comprehensive scores by the
+        exact route (hq_comp_scores on the gathered frames), a stable order by score descending (ties keep the
+        cascade's order), score >= threshold, the first k -> device (scores [Q, k] f64, ids [Q, k] i64), -inf / -1
+        padded.  One scoring launch per query.  ValueError with the reference's message when a query and a candidate
+        with index rows differ in index width."""
+        t = torch()
+        k = int(k)
+        if k < 1:
+            raise ValueError(f"k = {k}")
+        if self._frames is None:
+            raise ValueError("HierarchicalFrameCorpus.search needs the raw frames for the comprehensive re-rank: "
+                             "build the corpus with keep_frames=True")
+        q3, dq_dev, qr = self._queries(queries)
+        Q = qr.N
+        if q3.dtype != self.dtype:
+            q3 = q3.to(self.dtype)
+            dq_dev = K.comp_describe(q3)
+        dq = to_np(dq_dev)
+        out_s = np.full((Q, k), -np.inf)
+        out_i = np.full((Q, k), -1, dtype=np.int64)
+        if 2 * k <= K.HIER_MAX_K:
+            _, ids, _, _ = K.hier_filter(qr, self._rows, self._thr, self._ratio, 2 * k)
+            heads = [r[r >= 0] for r in to_np(ids)]
+        else:
+            heads = [self._candidates(qr, a)[:2 * k] for a in range(Q)]
+        for a, head in enumerate(heads):
+            if not len(head):
+                continue
+            sel = t.as_tensor(head, device=q3.device)
+            sc = to_np(_comp_exact(q3[a:a + 1], dq_dev[a:a + 1].contiguous(), dq[a:a + 1], self._frames[sel],
+                                   self._desc_dev[sel].contiguous(), self._desc[head]))[0]
+            order = np.argsort(-sc, kind="stable")
+            order = order[sc[order] >= threshold][:k]
+            out_s[a, :len(order)], out_i[a, :len(order)] = sc[order], head[order]
+        return to_dev(out_s), to_dev(out_i)
+
+
+def progressive_hierarchical_search(query_embedding, candidate_embeddings) -> List[int]:
+    """Drop-in for engine.py:51-95 with the store passed in (the reference reads it from
+    _get_all_candidate_embeddings): the candidate frame numbers after the progressive cascade, in its order.  An
+    empty or 1-D query and an empty store return [] as the reference does."""
+    q = np.asarray(query_embedding)
+    if q.size == 0 or q.ndim != 2 or len(candidate_embeddings) == 0:
+        return []
+    c = np.stack([np.asarray(x) for x in candidate_embeddings])
+    if c.ndim != 3 or c.shape[1:] != q.shape:
+        raise ValueError(f"candidate frames {c.shape[1:]} are not the query's {q.shape}")
+    return HierarchicalFrameCorpus(c, keep_frames=False).candidates(q)

@@ -798,6 +798,37 @@ int hq_comp_padded_k(int H, int W, int h);
 int hq_comp_prepare(const float* imgs, int64_t N, int64_t ld, int H, int W, int h, int side, const double* level_coef,
                     void* X16, double* inv, hq_stream_t stream);
 
+/* ---- S7: the progressive hierarchical search (rag/search/engine.py:51-95, 178-287, hq_hier.hip) ---
+ * The candidate cascade the engine runs before the comprehensive score, for a query batch against a prepared,
+ * resident corpus.  A frame's levels are its non-zero index rows below the detected height, in order (all-zero rows
+ * dropped, later rows move up), each cut after its last non-zero value.  Level score s_l(q, c), l < L_q: 0.0 when c
+ * has no level l, else (cos + 1) / 2 over the first min(len_q, len_c) values of the two rows, 0.0 when either
+ * truncated norm is 0; float64 sums in element order, so bit-identical frames score bit-identically.  At level l the
+ * survivors (every frame at level 0) are ordered by (s_l desc, s_{l-1} desc, ..., s_0 desc, id asc) — what the
+ * reference's stable sort per level amounts to — and the first cap_l = max(1, (int64)(n_prev * ratio[l])) of those
+ * with s_l >= thr[l] survive (n_prev: survivors entering the level, N at level 0).  A NaN score never passes.
+ * hq_hier_prepare: frames imgs [N, H, W] (float32 / float64, frame stride ld) and their hq_comp_describe
+ *   descriptors -> rows f64 [N, max_levels, W] (zero beyond each length and for missing levels) and lens int32
+ *   [N, max_levels] (0: no such level).  One launch.  1 <= max_levels <= 8; a frame with more non-zero index rows:
+ *   HQ_E_UNSUPPORTED (for H - 1 > max_levels the call reads one flag back and synchronises the stream).
+ * hq_hier_workspace_size: bytes hq_hier_filter needs: max_levels * Q * N float64 scores and Q * N bytes.
+ * hq_hier_filter: Lq int32 [Q] = the queries' level counts; thr, ratio: host tables of max_levels doubles.  Two
+ *   launches (all level scores; one workgroup per query for the cuts and the list head), no host round trip.
+ *   out_count [Q, max_levels] int64: survivors after each level, 0 for the levels the cascade did not run (l >= L_q,
+ *   or nobody was left).  out_top_ids [Q, kout] int64: the first kout of the final list in its order, -1 padded;
+ *   out_top_scores [Q, kout, max_levels]: their level scores (0.0 for l >= L_q and for pad entries).  out_alive
+ *   [Q, N] uint8 (NULL allowed): the number of levels each frame survived (the final list: == L_q).  A query with
+ *   L_q = 0 returns nothing; one with L_q > max_levels returns nothing either (no frame has level max_levels), its
+ *   counts are those of the max_levels levels run.  kout <= 64, W <= 512 (HQ_E_UNSUPPORTED beyond).  Q = 0 or N = 0:
+ *   returns 0 and writes only counts.                                                                        */
+int hq_hier_prepare(int dtype, const void* imgs, int64_t N, int64_t ld, int H, int W, const int32_t* desc,
+                    int max_levels, double* rows, int32_t* lens, hq_stream_t stream);
+size_t hq_hier_workspace_size(int Q, int64_t N, int max_levels);
+int hq_hier_filter(const double* q_rows, const int32_t* q_lens, const int32_t* Lq, int Q, const double* c_rows,
+                   const int32_t* c_lens, int64_t N, int W, int max_levels, const double* thr, const double* ratio,
+                   int kout, void* ws, int64_t* out_count, int64_t* out_top_ids, double* out_top_scores,
+                   uint8_t* out_alive, hq_stream_t stream);
+
 /* ---- §8e: the sharded search's one collective (RCCL over xGMI) ----------------------------------
  * The corpus is split into contiguous global-id ranges, one per GPU (one process per GPU); each rank
  * answers the whole query batch against its shard and packs fixed-size top-k records, and ONE
