@@ -4061,6 +4061,14 @@ __global__ __launch_bounds__(256) void k_cosine(const float* __restrict__ A, int
   }
 }
 
+// workgroups of a grid-stride launch: ceil(work / per_block), at most cap
+static unsigned grid_for(int64_t work, int per_block, int64_t cap) {
+  const int64_t b = (work + per_block - 1) / per_block;
+  return (unsigned)(b < cap ? b : cap);
+}
+// one workgroup per query, at most cap
+static int query_grid(int Q, int cap = 8192) { return Q < cap ? Q : cap; }
+
 static int rs_for(int kp) {
   int r = kp < 2 ? 2 : kp;
   while ((r % 32) != 2) ++r;
@@ -4224,18 +4232,15 @@ static int scan0_run(const double* Sq, const _Float16* Zq16, const float* Sq32, 
   hipLaunchKernelGGL(k_sample_topg, dim3(sa.nqb * sa.nchunks), dim3(64), 0, s, sa);
   HQ_CHECK_LAUNCH();
   // (k_sample_kth clears pool_n per query: no memset)
-  const int mg = Q < 8192 ? Q : 8192;
-  launch_kth(mg, s, (const float*)sa.top, 4 * sa.nchunks, Q, sample_kth, (double)kMarginF, th0, b.pool_n, Sq32, thr0,
-             b.inv_m, qc);
+  launch_kth(query_grid(Q), s, (const float*)sa.top, 4 * sa.nchunks, Q, sample_kth, (double)kMarginF, th0, b.pool_n,
+             Sq32, thr0, b.inv_m, qc);
   HQ_CHECK_LAUNCH();
   if (corpus_flags) {  // the corpus's flagged rows listed once (hq_seg_flag_rows): [count, rows...]
     flag_n = const_cast<int*>(corpus_flags);
     flag_list = flag_n + 1;
   } else {
     HQ_CHECK_HIP(hipMemsetAsync(flag_n, 0, sizeof(int), s));
-    const int64_t fb = (N + 255) / 256;
-    hipLaunchKernelGGL(k_flag_rows, dim3((unsigned)(fb < 4096 ? fb : 4096)), dim3(256), 0, s, Sc32, N, flag_list,
-                       flag_n);
+    hipLaunchKernelGGL(k_flag_rows, dim3(grid_for(N, 256, 4096)), dim3(256), 0, s, Sc32, N, flag_list, flag_n);
     HQ_CHECK_LAUNCH();
   }
   hipLaunchKernelGGL(k_scan0g, dim3(b.nqb * b.nchunks), dim3(64), 0, s, b);
@@ -4394,76 +4399,113 @@ static int launch_scan(const ScanArgs& a, hipStream_t s) {
 
 // exact re-rank launcher: the LDS-staged kernel when the staged rows fit (<= 96 KiB), else k_refine
 // (which has no re-score output: odet then takes hq_rescore's kernel afterwards)
-static int refine_launch(const double* Rq, const double* Zq, const double* Sq, int Q, const double* Rc,
-                         const double* Zc, const double* Sc, int64_t N, int L, int mode, const double* cand_score,
-                         const int64_t* cand_id, int kp, int k, double threshold, int thr_mode, double eps,
-                         int64_t id_base, double* out_score, int64_t* out_id, int* out_count, int* out_resolved,
-                         int count_empty, int* out_redo, double* out_det, hq_stream_t stream,
-                         int* next_redo = nullptr, void* workspace = nullptr, size_t workspace_bytes = 0,
-                         const FinalOut* fin = nullptr) {
+// One exact re-rank call: what the five hq_refine_* entries pass on.  The entries' optional arguments are
+// null / 0 where an entry has none.
+struct RefineCall {
+  VecSet q; int Q;
+  VecSet c; int64_t N;
+  int L, mode;
+  const double* cand_score; const int64_t* cand_id; int kp, k;
+  double threshold; int thr_mode; double eps; int64_t id_base;
+  double* out_score; int64_t* out_id; int* out_count; int* out_resolved;
+  int count_empty; int* out_redo;
+  hq_stream_t stream;
+  double* out_det = nullptr;
+  int* next_redo = nullptr;
+  void* workspace = nullptr; size_t workspace_bytes = 0;
+  const FinalOut* fin = nullptr;  // hq_refine_final_ws: the fused final ranking
+};
+
+// what an entry requires beyond the common buffers
+enum : unsigned {
+  kNeedDet = 1,       // out_det
+  kNeedCounters = 2,  // out_redo and next_redo
+  kListsOptional = 4  // out_score and out_id may both be null
+};
+
+// The entries' argument tests, in their order: sizes, (fused final ranking: a cooperative shape), Q = 0, null
+// buffers, workspace size.  HQ_OK with Q = 0: nothing is to be launched.
+static int refine_check(const RefineCall& c, unsigned need) {
+  const bool bad = c.Q < 0 || c.N < 0 || c.L <= 0 || c.kp <= 0 || c.kp > kMaxTopKBig || c.k <= 0 || c.k > c.kp;
+  if (c.fin) {
+    if (bad || c.fin->K <= 0) return fail(HQ_E_INVALID, "bad sizes kp=%d k=%d K=%d", c.kp, c.k, c.fin->K);
+  } else if (bad) {
+    return fail(HQ_E_INVALID, "bad sizes kp=%d k=%d", c.kp, c.k);
+  }
+  bool ws = c.workspace != nullptr;  // whether the workspace is used, so its size tested
+  if (c.fin) {
+    SegInfo si;
+    seg_info(c.L, si);
+    // the fused form exists on the lane-cooperative paths only (k_rank_small for lists <= 64, k_rank_pairs +
+    // k_rank_sort above; the caller keeps the two-step form otherwise: hq_refine_topk_ws + hq_progressive_final_ex)
+    const bool small = c.kp <= kMaxTopK && coop_ppl(si) && opt(OPT_REFINE_SMALL, 1) != 0;
+    ws = c.kp > kMaxTopK && coop_ppl(si) && opt(OPT_REFINE_COOP, 1) != 0 && c.Q <= 65535;
+    if (!small && !ws) return fail(HQ_E_UNSUPPORTED, "fused final ranking: kp=%d L=%d", c.kp, c.L);
+  }
+  if (c.Q == 0) {  // no kernel runs: the next batch's counter is still cleared
+    if (c.next_redo) HQ_CHECK_HIP(hipMemsetAsync(c.next_redo, 0, sizeof(int), (hipStream_t)c.stream));
+    return HQ_OK;
+  }
+  const bool lists = (need & kListsOptional) ? !c.out_score == !c.out_id : c.out_score && c.out_id;
+  if (!c.q.raw || !c.q.Z || !c.q.S || !c.cand_score || !c.cand_id || !lists || !c.out_count || !c.out_resolved ||
+      ((need & kNeedDet) && !c.out_det) || ((need & kNeedCounters) && (!c.out_redo || !c.next_redo)) ||
+      (c.next_redo && (!c.out_redo || c.out_redo == c.next_redo)) ||
+      (c.fin && (!c.fin->id || !c.fin->det || !c.fin->count)) || (ws && !c.workspace) ||
+      (c.N > 0 && (!c.c.raw || !c.c.Z || !c.c.S)))
+    return fail(HQ_E_INVALID, "null buffer");
+  if (ws && c.workspace_bytes < refine_ws_bytes(c.Q, c.kp, c.L)) return fail(HQ_E_INVALID, "workspace too small");
+  return HQ_OK;
+}
+
+// exact re-rank launcher: the LDS-staged kernel when the staged rows fit (<= 96 KiB), else k_refine
+// (which has no re-score output: odet then takes hq_rescore's kernel afterwards)
+static int refine_launch(const RefineCall& c) {
   SegInfo si;
-  seg_info(L, si);
-  const hipStream_t s = (hipStream_t)stream;
-  const int grid = Q < 8192 ? Q : 8192;
+  seg_info(c.L, si);
+  const hipStream_t s = (hipStream_t)c.stream;
+  const int Q = c.Q, kp = c.kp;
+  const dim3 grid(query_grid(Q));
+  const int ce = c.count_empty ? 1 : 0;
   // next_redo (hq_refine_rescore_topk_pp): out_redo arrives zeroed (cleared by the previous batch's kernel),
   // the kernel clears next_redo for the next batch; otherwise one 4-byte memset here
-  if (out_redo && !next_redo) HQ_CHECK_HIP(hipMemsetAsync(out_redo, 0, sizeof(int), s));
+  if (c.out_redo && !c.next_redo) HQ_CHECK_HIP(hipMemsetAsync(c.out_redo, 0, sizeof(int), s));
   const bool sm = seg_small(si);
   auto rank_args = [&]() {
     RankArgs ra;
-    ra.Rq = Rq; ra.Zq = Zq; ra.Sq = Sq; ra.Q = Q; ra.Rc = Rc; ra.Sc = Sc; ra.N = N;
+    ra.Rq = c.q.raw; ra.Zq = c.q.Z; ra.Sq = c.q.S; ra.Q = Q; ra.Rc = c.c.raw; ra.Sc = c.c.S; ra.N = c.N;
     ra.cs.nseg = si.nseg; ra.cs.L = si.L; ra.cs.Lp = si.Lp;
     for (int i = 0; i < kCoopMaxW - 1; ++i) {
       ra.cs.src[i] = i < si.nseg ? si.src[i] : 0;
       ra.cs.len[i] = i < si.nseg ? si.len[i] : 0;
       ra.cs.poff[i] = i < si.nseg ? si.poff[i] : 0;
     }
-    ra.mode = mode; ra.kp = kp; ra.k = k; ra.thr_mode = thr_mode; ra.det = out_det ? 1 : 0; ra.thr = threshold;
-    ra.id_base = id_base; ra.cid = cand_id;
+    ra.mode = c.mode; ra.kp = kp; ra.k = c.k; ra.thr_mode = c.thr_mode; ra.det = c.out_det ? 1 : 0;
+    ra.thr = c.threshold; ra.id_base = c.id_base; ra.cid = c.cand_id;
     ra.ws_sc = nullptr; ra.ws_id = nullptr; ra.ws_rec = nullptr;
     ra.win = (int)opt(OPT_RANK_WIN, 1);
     return ra;
   };
+  // the cooperative kernels' final ranking (hq_refine_final_ws) writes the records itself
+  const FinalOut fo = c.fin ? *c.fin : FinalOut{0, nullptr, nullptr, nullptr, 0};
+  double* odet = c.fin ? nullptr : c.out_det;
   // short lists: the fused lane-cooperative re-rank (k_rank_small) where its shapes hold; option
   // refine_small = 0 keeps k_refine_lds below (A/B, parity)
   if (kp <= kMaxTopK && coop_ppl(si) && opt(OPT_REFINE_SMALL, 1) != 0) {
     const RankArgs ra = rank_args();
     const int ng = kp <= 32 ? 32 : 64, W = 1 + si.nseg;
     const size_t lds = 8 * ((size_t)coop_qw(ra.cs) + (size_t)ng * coop_rw(ra.cs) + (size_t)ng * (2 + W)) + 8 * (size_t)ng;
-    const FinalOut fo = fin ? *fin : FinalOut{0, nullptr, nullptr, nullptr, 0};
-    double* odet_s = fin ? nullptr : out_det;
     const int ppl = coop_ppl(si);
-    const void* fn = ng == 32 ? (ppl == 6 ? (const void*)k_rank_small<6, 32> : (const void*)k_rank_small<10, 32>)
-                              : (ppl == 6 ? (const void*)k_rank_small<6, 64> : (const void*)k_rank_small<10, 64>);
-    if (lds > 65536) HQ_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int c = count_empty ? 1 : 0;
+    auto kern = ng == 32 ? (ppl == 6 ? k_rank_small<6, 32> : k_rank_small<10, 32>)
+                         : (ppl == 6 ? k_rank_small<6, 64> : k_rank_small<10, 64>);
     // compile-time level structures (L = 64, 32) here only with option rank_ct 2: at the 128-VGPR cap of this
     // kernel the unrolled scorer spills (28 VGPRs for L = 64)
     const int lid = ppl == 6 && opt(OPT_RANK_CT, 1) == 2 ? coop_lid(ra.cs) : 0;
-    if (lid == 1 && ng == 32)
-      hipLaunchKernelGGL((k_rank_small<6, 32, 1>), dim3(grid), dim3(256), lds, s, ra, cand_score, eps, out_score, out_id,
-                         out_count, out_resolved, c, out_redo, odet_s, next_redo, fo);
-    else if (lid == 2 && ng == 32)
-      hipLaunchKernelGGL((k_rank_small<6, 32, 2>), dim3(grid), dim3(256), lds, s, ra, cand_score, eps, out_score, out_id,
-                         out_count, out_resolved, c, out_redo, odet_s, next_redo, fo);
-    else if (lid == 1)
-      hipLaunchKernelGGL((k_rank_small<6, 64, 1>), dim3(grid), dim3(512), lds, s, ra, cand_score, eps, out_score, out_id,
-                         out_count, out_resolved, c, out_redo, odet_s, next_redo, fo);
-    else if (lid == 2)
-      hipLaunchKernelGGL((k_rank_small<6, 64, 2>), dim3(grid), dim3(512), lds, s, ra, cand_score, eps, out_score, out_id,
-                         out_count, out_resolved, c, out_redo, odet_s, next_redo, fo);
-    else if (ng == 32 && ppl == 6)
-      hipLaunchKernelGGL((k_rank_small<6, 32>), dim3(grid), dim3(256), lds, s, ra, cand_score, eps, out_score, out_id,
-                         out_count, out_resolved, c, out_redo, odet_s, next_redo, fo);
-    else if (ng == 32)
-      hipLaunchKernelGGL((k_rank_small<10, 32>), dim3(grid), dim3(256), lds, s, ra, cand_score, eps, out_score, out_id,
-                         out_count, out_resolved, c, out_redo, odet_s, next_redo, fo);
-    else if (ppl == 6)
-      hipLaunchKernelGGL((k_rank_small<6, 64>), dim3(grid), dim3(512), lds, s, ra, cand_score, eps, out_score, out_id,
-                         out_count, out_resolved, c, out_redo, odet_s, next_redo, fo);
-    else
-      hipLaunchKernelGGL((k_rank_small<10, 64>), dim3(grid), dim3(512), lds, s, ra, cand_score, eps, out_score, out_id,
-                         out_count, out_resolved, c, out_redo, odet_s, next_redo, fo);
+    if (lid && ng == 32) kern = lid == 1 ? k_rank_small<6, 32, 1> : k_rank_small<6, 32, 2>;
+    else if (lid) kern = lid == 1 ? k_rank_small<6, 64, 1> : k_rank_small<6, 64, 2>;
+    if (lds > 65536)
+      HQ_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, grid, dim3(8 * ng), lds, s, ra, c.cand_score, c.eps, c.out_score, c.out_id, c.out_count,
+                       c.out_resolved, ce, c.out_redo, odet, c.next_redo, fo);
     HQ_CHECK_LAUNCH();
     return HQ_OK;
   }
@@ -4472,77 +4514,66 @@ static int refine_launch(const double* Rq, const double* Zq, const double* Sq, i
     // entry, rows staged per group, every level in one pass) + the per-query ranking (k_rank_sort) where
     // its shapes hold; option refine_coop = 0 keeps the one-thread-per-entry kernels below (A/B, parity)
     const int ppl = coop_ppl(si);
-    if (workspace && ppl && opt(OPT_REFINE_COOP, 1) != 0 && Q <= 65535) {
-      if (workspace_bytes < refine_ws_bytes(Q, kp, L)) return fail(HQ_E_INVALID, "workspace too small");
+    if (c.workspace && ppl && opt(OPT_REFINE_COOP, 1) != 0 && Q <= 65535) {  // (its size: refine_check)
       RankArgs ra = rank_args();
-      uint8_t* w = reinterpret_cast<uint8_t*>(workspace);
+      uint8_t* w = reinterpret_cast<uint8_t*>(c.workspace);
       ra.ws_sc = reinterpret_cast<double*>(w);
       ra.ws_id = reinterpret_cast<int64_t*>(w + (size_t)Q * kp * 8);
       ra.ws_rec = reinterpret_cast<double*>(w + (size_t)Q * kp * 16);
       const size_t lds = 8 * ((size_t)coop_qw(ra.cs) + (size_t)kCoopGroups * coop_rw(ra.cs));
       // (round 6: two or four entries per group with the next row in flight measured 5-10% slower at M = 100 /
       // 1000 — profiles/r06_ab_count_read.txt, rank_e rows — the kernel was dropped)
-      {
-        const dim3 g1((kp + kCoopGroups - 1) / kCoopGroups, Q);
-        const int lid = ppl == 6 ? coop_lid(ra.cs) : 0;  // compile-time level structures (L = 64, 32)
-        if (lid == 1) hipLaunchKernelGGL((k_rank_pairs<6, 1>), g1, dim3(256), lds, s, ra);
-        else if (lid == 2) hipLaunchKernelGGL((k_rank_pairs<6, 2>), g1, dim3(256), lds, s, ra);
-        else if (ppl == 6) hipLaunchKernelGGL(k_rank_pairs<6>, g1, dim3(256), lds, s, ra);
-        else hipLaunchKernelGGL(k_rank_pairs<10>, g1, dim3(256), lds, s, ra);
-      }
+      const int lid = ppl == 6 ? coop_lid(ra.cs) : 0;  // compile-time level structures (L = 64, 32)
+      auto pairs = k_rank_pairs<6, 1>;
+      if (lid == 2) pairs = k_rank_pairs<6, 2>;
+      else if (lid != 1) pairs = ppl == 6 ? k_rank_pairs<6> : k_rank_pairs<10>;
+      hipLaunchKernelGGL(pairs, dim3((kp + kCoopGroups - 1) / kCoopGroups, Q), dim3(256), lds, s, ra);
       HQ_CHECK_LAUNCH();
-      const FinalOut fo = fin ? *fin : FinalOut{0, nullptr, nullptr, nullptr, 0};
-      double* od = fin ? nullptr : out_det;
-      const int ce = count_empty ? 1 : 0;
       // lists > 512: 256 threads, four entries each (4 queries per CU at 118 VGPRs: M = 1000 1.70 -> 1.76M QPS,
       // profiles/r06_ab_rank_win.txt); option rank_sort_nt 512: one compare-exchange per thread and stage
-      if (pow2_at_least(kp) <= 128 && opt(OPT_RANK_SORT_SMALL, 1) != 0)
-        hipLaunchKernelGGL((k_rank_sort<128, 128>), dim3(grid), dim3(128), 0, s, ra, cand_score, eps, out_score,
-                           out_id, out_count, out_resolved, ce, out_redo, od, next_redo, fo);
-      else if (kp > 512 && opt(OPT_RANK_SORT_NT, 256) == 512)
-        hipLaunchKernelGGL(k_rank_sort<512>, dim3(grid), dim3(512), 0, s, ra, cand_score, eps, out_score, out_id,
-                           out_count, out_resolved, ce, out_redo, od, next_redo, fo);
-      else
-        hipLaunchKernelGGL(k_rank_sort<256>, dim3(grid), dim3(256), 0, s, ra, cand_score, eps, out_score, out_id,
-                           out_count, out_resolved, ce, out_redo, od, next_redo, fo);
+      const bool narrow = pow2_at_least(kp) <= 128 && opt(OPT_RANK_SORT_SMALL, 1) != 0;
+      const bool wide = !narrow && kp > 512 && opt(OPT_RANK_SORT_NT, 256) == 512;
+      auto sort = k_rank_sort<128, 128>;
+      if (!narrow) sort = wide ? k_rank_sort<512> : k_rank_sort<256>;
+      hipLaunchKernelGGL(sort, grid, dim3(narrow ? 128 : wide ? 512 : 256), 0, s, ra, c.cand_score, c.eps, c.out_score, c.out_id, c.out_count,
+                         c.out_resolved, ce, c.out_redo, odet, c.next_redo, fo);
       HQ_CHECK_LAUNCH();
       return HQ_OK;
     }
     // lists of >= 512: the candidates' raw rows only (refine_big_body's ZB)
     const bool raw = kp >= 512;
     auto kern = sm ? (raw ? k_refine_big_sm_raw : k_refine_big_sm) : (raw ? k_refine_big_raw : k_refine_big);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, VecSet{Rq, Zq, Sq}, Q, VecSet{Rc, Zc, Sc}, N, si, mode,
-                       cand_score, cand_id, kp, k, threshold, thr_mode, eps, id_base, out_score, out_id, out_count,
-                       out_resolved, count_empty ? 1 : 0, out_redo, out_det, next_redo, 0);
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, c.q, Q, c.c, c.N, si, c.mode, c.cand_score, c.cand_id, kp, c.k,
+                       c.threshold, c.thr_mode, c.eps, c.id_base, c.out_score, c.out_id, c.out_count, c.out_resolved,
+                       ce, c.out_redo, c.out_det, c.next_redo, 0);
     HQ_CHECK_LAUNCH();
     return HQ_OK;
   }
   const size_t lds = ((size_t)refine_qw(si) + (size_t)kp * refine_rw(si) + (size_t)kp * (1 + si.nseg)) * 8;
-  if (lds <= 96 * 1024 && L % 2 == 0 && !opt_on(OPT_REFINE_GLOBAL)) {  // 16-B pieces: L even
-    const void* fn = sm ? (const void*)k_refine_lds_sm : (const void*)k_refine_lds;
-    HQ_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (sm)
-      hipLaunchKernelGGL(k_refine_lds_sm, dim3(grid), dim3(256), lds, s, VecSet{Rq, Zq, Sq}, Q, VecSet{Rc, Zc, Sc},
-                         N, si, mode, cand_score, cand_id, kp, k, threshold, thr_mode, eps, id_base, out_score, out_id,
-                         out_count, out_resolved, count_empty ? 1 : 0, out_redo, out_det, next_redo);
-    else
-      hipLaunchKernelGGL(k_refine_lds, dim3(grid), dim3(256), lds, s, VecSet{Rq, Zq, Sq}, Q, VecSet{Rc, Zc, Sc},
-                         N, si, mode, cand_score, cand_id, kp, k, threshold, thr_mode, eps, id_base, out_score, out_id,
-                         out_count, out_resolved, count_empty ? 1 : 0, out_redo, out_det, next_redo);
+  if (lds <= 96 * 1024 && c.L % 2 == 0 && !opt_on(OPT_REFINE_GLOBAL)) {  // 16-B pieces: L even
+    auto kern = sm ? k_refine_lds_sm : k_refine_lds;
+    HQ_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, c.q, Q, c.c, c.N, si, c.mode, c.cand_score, c.cand_id, kp, c.k,
+                       c.threshold, c.thr_mode, c.eps, c.id_base, c.out_score, c.out_id, c.out_count, c.out_resolved,
+                       ce, c.out_redo, c.out_det, c.next_redo);
     HQ_CHECK_LAUNCH();
     return HQ_OK;
   }
-  if (sm)
-    hipLaunchKernelGGL(k_refine<true>, dim3(grid), dim3(64), 0, s, VecSet{Rq, Zq, Sq}, Q, VecSet{Rc, Zc, Sc}, N, si,
-                       mode, cand_score, cand_id, kp, k, threshold, thr_mode, eps, id_base, out_score, out_id, out_count,
-                       out_resolved, count_empty ? 1 : 0, out_redo, next_redo);
-  else
-    hipLaunchKernelGGL(k_refine<false>, dim3(grid), dim3(64), 0, s, VecSet{Rq, Zq, Sq}, Q, VecSet{Rc, Zc, Sc}, N, si,
-                       mode, cand_score, cand_id, kp, k, threshold, thr_mode, eps, id_base, out_score, out_id, out_count,
-                       out_resolved, count_empty ? 1 : 0, out_redo, next_redo);
+  auto kern = sm ? k_refine<true> : k_refine<false>;
+  hipLaunchKernelGGL(kern, grid, dim3(64), 0, s, c.q, Q, c.c, c.N, si, c.mode, c.cand_score, c.cand_id, kp, c.k,
+                     c.threshold, c.thr_mode, c.eps, c.id_base, c.out_score, c.out_id, c.out_count, c.out_resolved, ce,
+                     c.out_redo, c.next_redo);
   HQ_CHECK_LAUNCH();
-  if (out_det) return hq_rescore(Rq, Zq, Sq, Q, Rc, Zc, Sc, N, L, out_id, k, id_base, out_det, stream);
+  if (c.out_det)
+    return hq_rescore(c.q.raw, c.q.Z, c.q.S, Q, c.c.raw, c.c.Z, c.c.S, c.N, c.L, c.out_id, c.k, c.id_base, c.out_det,
+                      c.stream);
   return HQ_OK;
+}
+
+// an entry's body after it has filled the call: the tests, then the launch unless nothing is to run
+static int refine_run(const RefineCall& c, unsigned need) {
+  const int rc = refine_check(c, need);
+  return rc != HQ_OK || c.Q == 0 ? rc : refine_launch(c);
 }
 
 
@@ -4642,6 +4673,42 @@ static bool ov_layout(int L, OvLayout& o) {
   else if (match(OvT<1>::NKB, OvT<1>::NG, OvT<1>::NC, [](int i) { return OvT<1>::kb(i); })) o.lid = 1;
   return o.lid >= 0;
 }
+
+// The optional split copies of a corpus that hq_seg_append, hq_seg_gather and hq_seg_replace keep in step
+// with its rows: level-0 (Z16, S32), overall (Zov16, Sov32) and the flagged-row list.
+struct SplitCopies {
+  _Float16* Z16;
+  float* S32;
+  _Float16* Zov16;
+  float* Sov32;
+  int* flags;
+};
+static SplitCopies split_copies(void* Z16, float* S32, void* Zov16, float* Sov32, int* flags) {
+  return {reinterpret_cast<_Float16*>(Z16), S32, reinterpret_cast<_Float16*>(Zov16), Sov32, flags};
+}
+
+// a copy comes with both of its buffers, the flagged-row list with the level-0 copies
+static int split_copies_paired(const SplitCopies& c) {
+  if ((c.Z16 == nullptr) != (c.S32 == nullptr) || (c.Zov16 == nullptr) != (c.Sov32 == nullptr))
+    return fail(HQ_E_INVALID, "a split copy needs both of its buffers");
+  if (c.flags && !c.S32) return fail(HQ_E_INVALID, "the flagged-row list needs the level-0 copies");
+  return HQ_OK;
+}
+
+// L has a level structure (si), and the layouts of the copies that are given (o: the overall one, else zeros)
+static int split_copies_check(int L, const SplitCopies& c, SegInfo& si, OvLayout& o) {
+  seg_info(L, si);
+  if (si.nseg == 0) return fail(HQ_E_INVALID, "no level structure for L=%d", L);
+  if (c.Z16 && si.plen[0] > 32)
+    return fail(HQ_E_INVALID, "level-0 copies with a level-0 segment of %d values", si.plen[0]);
+  o = {};
+  if (c.Zov16 && !ov_layout(L, o))
+    return fail(HQ_E_INVALID, "overall copies without a split overall layout (L=%d)", L);
+  return HQ_OK;
+}
+
+// the lane-cooperative row preparation where its shapes hold (option prep_coop = 0: the serial form)
+static bool prep_coop(const SegInfo& si) { return seg_small(si) && si.nseg <= 8 && opt(OPT_PREP_COOP, 1) != 0; }
 
 __host__ __device__ __forceinline__ int ov_gsize(int ng, int nc) { return 16 * ng + 4 * nc + 8; }
 // in a statistics group: one-value segment ci at 4 ci, the row flags at 4 nc, the rows' bound offsets at
@@ -5548,18 +5615,15 @@ static int ov_launch(const OvArgs& a0, const OvPlan& p, const SegInfo& si, int k
   // (a hi.hi step loop with the split G of the kept rows recomputed in the epilogue measured 139 vs 106 us)
   hipLaunchKernelGGL(k_sampleov<LID>, dim3(sa.nqb * sa.nchunks), dim3(64), 0, s, sa);
   HQ_CHECK_LAUNCH();
-  const int mg = Q < 8192 ? Q : 8192;
-  launch_kth(mg, s, (const float*)sa.top, 4 * sa.nchunks, Q, sample_kth, (double)kMarginF, th0,
+  launch_kth(query_grid(Q), s, (const float*)sa.top, 4 * sa.nchunks, Q, sample_kth, (double)kMarginF, th0,
              a.pool_n, (const float*)nullptr, thr0, 0.0, (QConst*)nullptr);
   HQ_CHECK_LAUNCH();
   hipLaunchKernelGGL(k_ov_qconst, dim3((Q + 255) / 256), dim3(256), 0, s, a.Sq32, Q, a.o, (const double*)th0, thr0, qc);
   HQ_CHECK_LAUNCH();
   // flagged rows (normally none), the scan, the pools' exact top k
   HQ_CHECK_HIP(hipMemsetAsync(flag_n, 0, sizeof(int), s));
-  const int64_t fb = (a.N + 255) / 256;
-  const int GS = ov_gsize(a.o.ng, a.o.nc);
-  hipLaunchKernelGGL(k_ov_flag_rows, dim3((unsigned)(fb < 4096 ? fb : 4096)), dim3(256), 0, s, a.Sc32, a.N, GS,
-                     4 * a.o.nc, flag_list, flag_n);
+  hipLaunchKernelGGL(k_ov_flag_rows, dim3(grid_for(a.N, 256, 4096)), dim3(256), 0, s, a.Sc32, a.N,
+                     ov_gsize(a.o.ng, a.o.nc), 4 * a.o.nc, flag_list, flag_n);
   HQ_CHECK_LAUNCH();
   if (k > kMaxTopK) {
     // the med3 + fma bound with pool appends straight to global memory: long lists (k > 64) pass more pairs
@@ -5597,9 +5661,8 @@ __global__ __launch_bounds__(256) void k_empty_lists(double* __restrict__ score,
 }
 
 static int empty_lists(double* score, int64_t* id, int Q, int k, double* best, int64_t* best_id, hipStream_t s) {
-  const int64_t n = (int64_t)Q * k, nb = (n + 255) / 256;  // n >= Q: the lists cover the arg-max entries
-  hipLaunchKernelGGL(k_empty_lists, dim3((unsigned)(nb < 4096 ? nb : 4096)), dim3(256), 0, s, score, id, n, best,
-                     best_id, Q);
+  const int64_t n = (int64_t)Q * k;  // n >= Q: the lists cover the arg-max entries
+  hipLaunchKernelGGL(k_empty_lists, dim3(grid_for(n, 256, 4096)), dim3(256), 0, s, score, id, n, best, best_id, Q);
   HQ_CHECK_LAUNCH();
   return HQ_OK;
 }
@@ -5666,15 +5729,12 @@ int hq_seg_prepare_rows(const double* idx, int64_t N, int L, int src_f32, const 
   SegInfo si;
   seg_info(L, si);
   if (si.nseg == 0) return fail(HQ_E_INVALID, "no level structure for L=%d", L);
-  const int64_t total = N * si.nseg;
   if (N <= 16384 && si.L <= 4096) {
     hipLaunchKernelGGL(k_seg_prepare_lds, dim3((unsigned)N), dim3(64), (size_t)8 * si.L, (hipStream_t)stream, idx, N,
                        si, src_f32 ? 1 : 0, row_f32, Z, stats);
   } else {
-    int64_t blocks = (total + 255) / 256;
-    if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(k_seg_prepare, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, idx, N, si,
-                       src_f32 ? 1 : 0, row_f32, Z, stats);
+    hipLaunchKernelGGL(k_seg_prepare, dim3(grid_for(N * si.nseg, 256, 16384)), dim3(256), 0, (hipStream_t)stream, idx,
+                       N, si, src_f32 ? 1 : 0, row_f32, Z, stats);
   }
   HQ_CHECK_LAUNCH();
   return HQ_OK;
@@ -5700,15 +5760,9 @@ int hq_level_scores(const double* Rq, const double* Zq, const double* Sq, int Q,
     HQ_CHECK_LAUNCH();
     return HQ_OK;
   }
-  const int64_t total = (int64_t)Q * N;
-  int64_t blocks = (total + 255) / 256;
-  if (blocks > 16384) blocks = 16384;
-  if (seg_small(si))
-    hipLaunchKernelGGL(k_level_scores<true>, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, VecSet{Rq, Zq, Sq}, Q,
-                     VecSet{Rc, Zc, Sc}, N, si, level, scores);
-  else
-    hipLaunchKernelGGL(k_level_scores<false>, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, VecSet{Rq, Zq, Sq}, Q,
-                     VecSet{Rc, Zc, Sc}, N, si, level, scores);
+  auto kern = seg_small(si) ? k_level_scores<true> : k_level_scores<false>;
+  hipLaunchKernelGGL(kern, dim3(grid_for((int64_t)Q * N, 256, 16384)), dim3(256), 0, (hipStream_t)stream,
+                     VecSet{Rq, Zq, Sq}, Q, VecSet{Rc, Zc, Sc}, N, si, level, scores);
   HQ_CHECK_LAUNCH();
   return HQ_OK;
 }
@@ -5718,14 +5772,9 @@ int hq_refine_topk(const double* Rq, const double* Zq, const double* Sq, int Q, 
                    int kp, int k, double threshold, int thr_mode, double eps, int64_t id_base, double* out_score,
                    int64_t* out_id, int* out_count, int* out_resolved, int count_empty, int* out_redo,
                    hq_stream_t stream) {
-  if (Q < 0 || N < 0 || L <= 0 || kp <= 0 || kp > kMaxTopKBig || k <= 0 || k > kp)
-    return fail(HQ_E_INVALID, "bad sizes kp=%d k=%d", kp, k);
-  if (Q == 0) return HQ_OK;
-  if (!Rq || !Zq || !Sq || !cand_score || !cand_id || !out_score || !out_id || !out_count || !out_resolved ||
-      (N > 0 && (!Rc || !Zc || !Sc)))
-    return fail(HQ_E_INVALID, "null buffer");
-  return refine_launch(Rq, Zq, Sq, Q, Rc, Zc, Sc, N, L, mode, cand_score, cand_id, kp, k, threshold, thr_mode, eps,
-                       id_base, out_score, out_id, out_count, out_resolved, count_empty, out_redo, nullptr, stream);
+  const RefineCall c{{Rq, Zq, Sq}, Q, {Rc, Zc, Sc}, N, L, mode, cand_score, cand_id, kp, k, threshold, thr_mode, eps,
+                     id_base, out_score, out_id, out_count, out_resolved, count_empty, out_redo, stream};
+  return refine_run(c, 0);
 }
 
 int hq_refine_rescore_topk_pp(const double* Rq, const double* Zq, const double* Sq, int Q, const double* Rc,
@@ -5734,18 +5783,10 @@ int hq_refine_rescore_topk_pp(const double* Rq, const double* Zq, const double* 
                               int thr_mode, double eps, int64_t id_base, double* out_score, int64_t* out_id,
                               int* out_count, int* out_resolved, int count_empty, int* out_redo, int* next_redo,
                               double* out_det, hq_stream_t stream) {
-  if (Q < 0 || N < 0 || L <= 0 || kp <= 0 || kp > kMaxTopKBig || k <= 0 || k > kp)
-    return fail(HQ_E_INVALID, "bad sizes kp=%d k=%d", kp, k);
-  if (Q == 0) {  // no kernel runs: the next batch's counter is still cleared
-    if (next_redo) HQ_CHECK_HIP(hipMemsetAsync(next_redo, 0, sizeof(int), (hipStream_t)stream));
-    return HQ_OK;
-  }
-  if (!Rq || !Zq || !Sq || !cand_score || !cand_id || !out_score || !out_id || !out_count || !out_resolved ||
-      !out_det || !out_redo || !next_redo || out_redo == next_redo || (N > 0 && (!Rc || !Zc || !Sc)))
-    return fail(HQ_E_INVALID, "null buffer");
-  return refine_launch(Rq, Zq, Sq, Q, Rc, Zc, Sc, N, L, mode, cand_score, cand_id, kp, k, threshold, thr_mode, eps,
-                       id_base, out_score, out_id, out_count, out_resolved, count_empty, out_redo, out_det, stream,
-                       next_redo);
+  const RefineCall c{{Rq, Zq, Sq}, Q, {Rc, Zc, Sc}, N, L, mode, cand_score, cand_id, kp, k, threshold, thr_mode, eps,
+                     id_base, out_score, out_id, out_count, out_resolved, count_empty, out_redo, stream, out_det,
+                     next_redo};
+  return refine_run(c, kNeedDet | kNeedCounters);
 }
 
 int hq_refine_rescore_topk(const double* Rq, const double* Zq, const double* Sq, int Q, const double* Rc,
@@ -5753,14 +5794,9 @@ int hq_refine_rescore_topk(const double* Rq, const double* Zq, const double* Sq,
                            const int64_t* cand_id, int kp, int k, double threshold, int thr_mode, double eps,
                            int64_t id_base, double* out_score, int64_t* out_id, int* out_count, int* out_resolved,
                            int count_empty, int* out_redo, double* out_det, hq_stream_t stream) {
-  if (Q < 0 || N < 0 || L <= 0 || kp <= 0 || kp > kMaxTopKBig || k <= 0 || k > kp)
-    return fail(HQ_E_INVALID, "bad sizes kp=%d k=%d", kp, k);
-  if (Q == 0) return HQ_OK;
-  if (!Rq || !Zq || !Sq || !cand_score || !cand_id || !out_score || !out_id || !out_count || !out_resolved ||
-      !out_det || (N > 0 && (!Rc || !Zc || !Sc)))
-    return fail(HQ_E_INVALID, "null buffer");
-  return refine_launch(Rq, Zq, Sq, Q, Rc, Zc, Sc, N, L, mode, cand_score, cand_id, kp, k, threshold, thr_mode, eps,
-                       id_base, out_score, out_id, out_count, out_resolved, count_empty, out_redo, out_det, stream);
+  const RefineCall c{{Rq, Zq, Sq}, Q, {Rc, Zc, Sc}, N, L, mode, cand_score, cand_id, kp, k, threshold, thr_mode, eps,
+                     id_base, out_score, out_id, out_count, out_resolved, count_empty, out_redo, stream, out_det};
+  return refine_run(c, kNeedDet);
 }
 
 size_t hq_refine_workspace_size(int Q, int kp, int L) { return refine_ws_bytes(Q, kp, L); }
@@ -5770,19 +5806,10 @@ int hq_refine_topk_ws(const double* Rq, const double* Zq, const double* Sq, int 
                       int kp, int k, double threshold, int thr_mode, double eps, int64_t id_base, double* out_score,
                       int64_t* out_id, int* out_count, int* out_resolved, int count_empty, int* out_redo,
                       int* next_redo, double* out_det, void* workspace, size_t workspace_bytes, hq_stream_t stream) {
-  if (Q < 0 || N < 0 || L <= 0 || kp <= 0 || kp > kMaxTopKBig || k <= 0 || k > kp)
-    return fail(HQ_E_INVALID, "bad sizes kp=%d k=%d", kp, k);
-  if (Q == 0) {  // no kernel runs: the next batch's counter is still cleared
-    if (next_redo) HQ_CHECK_HIP(hipMemsetAsync(next_redo, 0, sizeof(int), (hipStream_t)stream));
-    return HQ_OK;
-  }
-  if (!Rq || !Zq || !Sq || !cand_score || !cand_id || !out_score || !out_id || !out_count || !out_resolved ||
-      (next_redo && (!out_redo || out_redo == next_redo)) || (N > 0 && (!Rc || !Zc || !Sc)))
-    return fail(HQ_E_INVALID, "null buffer");
-  if (workspace && workspace_bytes < hq_refine_workspace_size(Q, kp, L)) return fail(HQ_E_INVALID, "workspace too small");
-  return refine_launch(Rq, Zq, Sq, Q, Rc, Zc, Sc, N, L, mode, cand_score, cand_id, kp, k, threshold, thr_mode, eps,
-                       id_base, out_score, out_id, out_count, out_resolved, count_empty, out_redo, out_det, stream,
-                       next_redo, workspace, workspace_bytes);
+  const RefineCall c{{Rq, Zq, Sq}, Q, {Rc, Zc, Sc}, N, L, mode, cand_score, cand_id, kp, k, threshold, thr_mode, eps,
+                     id_base, out_score, out_id, out_count, out_resolved, count_empty, out_redo, stream, out_det,
+                     next_redo, workspace, workspace_bytes};
+  return refine_run(c, 0);
 }
 
 int hq_refine_final_ws(const double* Rq, const double* Zq, const double* Sq, int Q, const double* Rc, const double* Zc,
@@ -5791,31 +5818,14 @@ int hq_refine_final_ws(const double* Rq, const double* Zq, const double* Sq, int
                        int64_t* out_id, int* out_count, int* out_resolved, int* out_redo, int* next_redo, int K_out,
                        int64_t* fin_id, double* fin_det, int* fin_count, void* workspace, size_t workspace_bytes,
                        hq_stream_t stream) {
-  if (Q < 0 || N < 0 || L <= 0 || kp <= 0 || kp > kMaxTopKBig || k <= 0 || k > kp || K_out <= 0)
-    return fail(HQ_E_INVALID, "bad sizes kp=%d k=%d K=%d", kp, k, K_out);
-  SegInfo si;
-  seg_info(L, si);
-  // the fused form exists on the lane-cooperative paths only (k_rank_small for lists <= 64, k_rank_pairs +
-  // k_rank_sort above; the caller keeps the two-step form otherwise: hq_refine_topk_ws + hq_progressive_final_ex)
-  const bool small = kp <= kMaxTopK && coop_ppl(si) && opt(OPT_REFINE_SMALL, 1) != 0;
-  const bool big = kp > kMaxTopK && coop_ppl(si) && opt(OPT_REFINE_COOP, 1) != 0 && Q <= 65535;
-  if (!small && !big) return fail(HQ_E_UNSUPPORTED, "fused final ranking: kp=%d L=%d", kp, L);
-  if (Q == 0) {
-    if (next_redo) HQ_CHECK_HIP(hipMemsetAsync(next_redo, 0, sizeof(int), (hipStream_t)stream));
-    return HQ_OK;
-  }
-  // out_score / out_id may both be null: the level-0 lists are then not written
-  if (!Rq || !Zq || !Sq || !cand_score || !cand_id || (!out_score != !out_id) || !out_count || !out_resolved ||
-      !fin_id || !fin_det || !fin_count || (big && !workspace) || (next_redo && (!out_redo || out_redo == next_redo)) ||
-      (N > 0 && (!Rc || !Zc || !Sc)))
-    return fail(HQ_E_INVALID, "null buffer");
-  if (big && workspace_bytes < hq_refine_workspace_size(Q, kp, L)) return fail(HQ_E_INVALID, "workspace too small");
   const FinalOut fin{K_out, fin_id, fin_det, fin_count, 1};
-  // records on (the final ranking reads them from the workspace), count_empty on (nothing passed: redo)
-  double* dummy_det = fin_det;
-  return refine_launch(Rq, Zq, Sq, Q, Rc, Zc, Sc, N, L, 0, cand_score, cand_id, kp, k, threshold, thr_mode, eps,
-                       id_base, out_score, out_id, out_count, out_resolved, 1, out_redo, dummy_det, stream, next_redo,
-                       workspace, workspace_bytes, &fin);
+  // mode 0; count_empty on (nothing passed: redo); out_det set (fin_det stands in): records on, the final
+  // ranking reads them from the workspace.  out_score / out_id may both be null: the level-0 lists are then
+  // not written
+  const RefineCall c{{Rq, Zq, Sq}, Q, {Rc, Zc, Sc}, N, L, 0, cand_score, cand_id, kp, k, threshold, thr_mode, eps,
+                     id_base, out_score, out_id, out_count, out_resolved, 1, out_redo, stream, fin_det, next_redo,
+                     workspace, workspace_bytes, &fin};
+  return refine_run(c, kListsOptional);
 }
 
 size_t hq_scan_workspace_size(int Q, int64_t N, int k) {
@@ -5873,8 +5883,7 @@ int hq_scan_topk(const double* Zq, const double* Sq, int Q, const double* Zc, co
     else return fail(HQ_E_UNSUPPORTED, "index too long for the fused scan (Lp=%d)", kp);
   }
   if (rc) return rc;
-  int mg = Q < 4096 ? Q : 4096;
-  hipLaunchKernelGGL(k_merge, dim3(mg), dim3(64), 0, s, a.ws_score, a.ws_id, a.ws_best, a.ws_best_id, a.nchunks, Q,
+  hipLaunchKernelGGL(k_merge, dim3(query_grid(Q, 4096)), dim3(64), 0, s, a.ws_score, a.ws_id, a.ws_best, a.ws_best_id, a.nchunks, Q,
                      k, out_score, out_id, out_best, out_best_id);
   HQ_CHECK_LAUNCH();
   return HQ_OK;
@@ -5895,18 +5904,9 @@ int hq_seg_prepare_pack0(const double* idx, int64_t N, int L, int src_f32, const
   if (si.nseg == 0) return fail(HQ_E_INVALID, "no level structure for L=%d", L);
   if (si.plen[0] > 32) return fail(HQ_E_UNSUPPORTED, "level-0 segment of %d values (<= 32)", si.plen[0]);
   if (si.L > 4096) return fail(HQ_E_UNSUPPORTED, "L=%d (<= 4096)", L);
-  const int64_t rows = z16_rows(N);
-  // default: the lane-cooperative form where its shapes hold (option prep_coop = 0: the serial form)
-  if (seg_small(si) && si.nseg <= 8 && opt(OPT_PREP_COOP, 1) != 0) {
-    hipLaunchKernelGGL(k_seg_prepare_pack0_coop, dim3((unsigned)(rows < 65536 ? rows : 65536)), dim3(64),
-                       (size_t)8 * si.L, (hipStream_t)stream, idx, N, si, src_f32 ? 1 : 0, row_f32, Z, stats,
-                       reinterpret_cast<_Float16*>(Z16), S32);
-    HQ_CHECK_LAUNCH();
-    return HQ_OK;
-  }
-  hipLaunchKernelGGL(k_seg_prepare_pack0, dim3((unsigned)(rows < 65536 ? rows : 65536)), dim3(64), (size_t)8 * si.L,
-                     (hipStream_t)stream, idx, N, si, src_f32 ? 1 : 0, row_f32, Z, stats,
-                     reinterpret_cast<_Float16*>(Z16), S32);
+  auto kern = prep_coop(si) ? k_seg_prepare_pack0_coop : k_seg_prepare_pack0;
+  hipLaunchKernelGGL(kern, dim3(grid_for(z16_rows(N), 1, 65536)), dim3(64), (size_t)8 * si.L, (hipStream_t)stream, idx,
+                     N, si, src_f32 ? 1 : 0, row_f32, Z, stats, reinterpret_cast<_Float16*>(Z16), S32);
   HQ_CHECK_LAUNCH();
   return HQ_OK;
 }
@@ -5919,10 +5919,8 @@ int hq_seg_pack0_split(const double* Z, const double* S, int64_t N, int L, void*
   seg_info(L, si);
   if (si.nseg == 0) return fail(HQ_E_INVALID, "no level structure for L=%d", L);
   if (si.plen[0] > 32) return fail(HQ_E_UNSUPPORTED, "level-0 segment of %d values (<= 32)", si.plen[0]);
-  int64_t blocks = (z16_rows(N) * 32 + 255) / 256;
-  if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(k_pack0, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, Z, S, N, si.Lp, si.plen[0],
-                     si.nseg, reinterpret_cast<_Float16*>(Z16), S32);
+  hipLaunchKernelGGL(k_pack0, dim3(grid_for(z16_rows(N) * 32, 256, 16384)), dim3(256), 0, (hipStream_t)stream, Z, S, N,
+                     si.Lp, si.plen[0], si.nseg, reinterpret_cast<_Float16*>(Z16), S32);
   HQ_CHECK_LAUNCH();
   return HQ_OK;
 }
@@ -5933,8 +5931,7 @@ int hq_seg_flag_rows(const float* S32, int64_t N, int* flags, hq_stream_t stream
   hipStream_t s = (hipStream_t)stream;
   HQ_CHECK_HIP(hipMemsetAsync(flags, 0, sizeof(int), s));
   if (N == 0) return HQ_OK;
-  const int64_t fb = (N + 255) / 256;
-  hipLaunchKernelGGL(k_flag_rows, dim3((unsigned)(fb < 4096 ? fb : 4096)), dim3(256), 0, s, S32, N, flags + 1, flags);
+  hipLaunchKernelGGL(k_flag_rows, dim3(grid_for(N, 256, 4096)), dim3(256), 0, s, S32, N, flags + 1, flags);
   HQ_CHECK_LAUNCH();
   return HQ_OK;
 }
@@ -5978,21 +5975,10 @@ int hq_rescore(const double* Rq, const double* Zq, const double* Sq, int Q, cons
   seg_info(L, si);
   const int64_t total = (int64_t)Q * k;
   const int G = si.nseg <= 8 ? 8 : 16;
-  int64_t blocks = (total * G + 255) / 256;
-  if (blocks > 16384) blocks = 16384;
   const bool sm = seg_small(si);
-  if (G == 8 && sm)
-    hipLaunchKernelGGL((k_rescore<8, true>), dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, VecSet{Rq, Zq, Sq},
-                       Q, VecSet{Rc, Zc, Sc}, N, si, ids, k, id_base, out);
-  else if (G == 8)
-    hipLaunchKernelGGL((k_rescore<8, false>), dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, VecSet{Rq, Zq, Sq},
-                       Q, VecSet{Rc, Zc, Sc}, N, si, ids, k, id_base, out);
-  else if (sm)
-    hipLaunchKernelGGL((k_rescore<16, true>), dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, VecSet{Rq, Zq, Sq},
-                       Q, VecSet{Rc, Zc, Sc}, N, si, ids, k, id_base, out);
-  else
-    hipLaunchKernelGGL((k_rescore<16, false>), dim3((int)blocks), dim3(256), 0, (hipStream_t)stream,
-                       VecSet{Rq, Zq, Sq}, Q, VecSet{Rc, Zc, Sc}, N, si, ids, k, id_base, out);
+  auto kern = G == 8 ? (sm ? k_rescore<8, true> : k_rescore<8, false>) : (sm ? k_rescore<16, true> : k_rescore<16, false>);
+  hipLaunchKernelGGL(kern, dim3(grid_for(total * G, 256, 16384)), dim3(256), 0, (hipStream_t)stream, VecSet{Rq, Zq, Sq},
+                     Q, VecSet{Rc, Zc, Sc}, N, si, ids, k, id_base, out);
   HQ_CHECK_LAUNCH();
   return HQ_OK;
 }
@@ -6013,7 +5999,7 @@ int hq_progressive_final_ex(int R, int Q, int M, int nseg, const double* s0, con
   if (!s0 || !ids || !det || !best || !best_id || !best_det || !out_id || !out_det || !out_count)
     return fail(HQ_E_INVALID, "null buffer");
   const int W = 1 + nseg;
-  const int grid = Q < 8192 ? Q : 8192;
+  const int grid = query_grid(Q);
   if (M <= kMaxTopK)
     hipLaunchKernelGGL(k_progressive_final, dim3(grid), dim3(64), 0, (hipStream_t)stream, R, Q, M, W, s0, ids, det,
                        best, best_id, best_det, K, out_id, out_det, out_count, flags);
@@ -6081,8 +6067,8 @@ int hq_select_topk_ws(const double* scores, int Q, int64_t N, int k, double thre
     // stage 1: parts of the row (the arg-maxes per part, or straight to the outputs when one part)
     const int64_t part1 = (N + P1 - 1) / P1;
     bool last = P1 == 1;
-    int64_t g = (int64_t)Q * P1 < 65536 ? (int64_t)Q * P1 : 65536;
-    hipLaunchKernelGGL(k_select_sort, dim3((unsigned)g), dim3(512), 0, s, scores, (const int64_t*)nullptr, Q, N, part1,
+    hipLaunchKernelGGL(k_select_sort, dim3(grid_for(Q * P1, 1, 65536)), dim3(512), 0, s, scores,
+                       (const int64_t*)nullptr, Q, N, part1,
                        (int)P1, k, threshold, thr_mode, last ? 1 : 0, id_base, last ? out_score : bs[0],
                        last ? out_id : bi[0], last ? out_best : pb, last ? out_best_id : pbi, (const double*)nullptr,
                        (const int64_t*)nullptr, 0);
@@ -6093,8 +6079,7 @@ int hq_select_topk_ws(const double* scores, int Q, int64_t N, int k, double thre
     while (P > 1) {
       const int64_t P2 = (P + F - 1) / F;
       last = P2 == 1;
-      g = (int64_t)Q * P2 < 65536 ? (int64_t)Q * P2 : 65536;
-      hipLaunchKernelGGL(k_select_sort, dim3((unsigned)g), dim3(512), 0, s, (const double*)bs[cur],
+      hipLaunchKernelGGL(k_select_sort, dim3(grid_for(Q * P2, 1, 65536)), dim3(512), 0, s, (const double*)bs[cur],
                          (const int64_t*)bi[cur], Q, P * k, F * k, (int)P2, k, threshold, thr_mode, last ? 1 : 0,
                          id_base, last ? out_score : bs[cur ^ 1], last ? out_id : bi[cur ^ 1],
                          last ? out_best : (double*)nullptr, last ? out_best_id : (int64_t*)nullptr,
@@ -6129,8 +6114,8 @@ int hq_select_topk_ws(const double* scores, int Q, int64_t N, int k, double thre
     // every stage keeps the arg-maxes (the final one writes them only when requested)
     int64_t P = P1;
     const bool last1 = P == 1;
-    int64_t g = (int64_t)Q * P < 65536 ? (int64_t)Q * P : 65536;
-    hipLaunchKernelGGL(k_select_reg1, dim3((unsigned)g), dim3(64), 0, s, scores, Q, N, (int)P, k, threshold, thr_mode,
+    hipLaunchKernelGGL(k_select_reg1, dim3(grid_for(Q * P, 1, 65536)), dim3(64), 0, s, scores, Q, N, (int)P, k,
+                       threshold, thr_mode,
                        last1 ? id_base : 0, last1 ? out_score : as, last1 ? out_id : ai, last1 ? out_best : ab,
                        last1 ? out_best_id : abi);
     HQ_CHECK_LAUNCH();
@@ -6142,8 +6127,7 @@ int hq_select_topk_ws(const double* scores, int Q, int64_t N, int k, double thre
       int64_t *ii, *ibi, *oi, *obi;
       if (cur == 0) { is_ = as; ii = ai; ib = ab; ibi = abi; os_ = bs_; oi = bi; ob = bb; obi = bbi; }
       else { is_ = bs_; ii = bi; ib = bb; ibi = bbi; os_ = as; oi = ai; ob = ab; obi = abi; }
-      g = (int64_t)Q * P2 < 65536 ? (int64_t)Q * P2 : 65536;
-      hipLaunchKernelGGL(k_select_regm, dim3((unsigned)g), dim3(64), 0, s, Q, (int)P, F, (int)P2, k,
+      hipLaunchKernelGGL(k_select_regm, dim3(grid_for(Q * P2, 1, 65536)), dim3(64), 0, s, Q, (int)P, F, (int)P2, k,
                          last ? id_base : 0, (const double*)is_, (const int64_t*)ii, (const double*)ib,
                          (const int64_t*)ibi, last ? out_score : os_, last ? out_id : oi, last ? out_best : ob,
                          last ? out_best_id : obi);
@@ -6164,12 +6148,10 @@ int hq_select_topk_ws(const double* scores, int Q, int64_t N, int k, double thre
   int64_t* ws_id = reinterpret_cast<int64_t*>(ws + nk * 8);
   double* ws_b = reinterpret_cast<double*>(ws + nk * 16);
   int64_t* ws_bid = reinterpret_cast<int64_t*>(ws + nk * 16 + (size_t)Q * P * 8);
-  const int64_t g1 = (int64_t)Q * P < 65536 ? (int64_t)Q * P : 65536;
-  hipLaunchKernelGGL(k_select_part, dim3((unsigned)g1), dim3(64), 0, (hipStream_t)stream, scores, Q, N, P, plen, k,
-                     threshold, thr_mode, ws_s, ws_id, ws_b, ws_bid);
+  hipLaunchKernelGGL(k_select_part, dim3(grid_for((int64_t)Q * P, 1, 65536)), dim3(64), 0, (hipStream_t)stream, scores,
+                     Q, N, P, plen, k, threshold, thr_mode, ws_s, ws_id, ws_b, ws_bid);
   HQ_CHECK_LAUNCH();
-  const int g2 = Q < 4096 ? Q : 4096;
-  hipLaunchKernelGGL(k_select_merge, dim3(g2), dim3(64), 0, (hipStream_t)stream, Q, P, k, threshold, thr_mode, id_base,
+  hipLaunchKernelGGL(k_select_merge, dim3(query_grid(Q, 4096)), dim3(64), 0, (hipStream_t)stream, Q, P, k, threshold, thr_mode, id_base,
                      (const double*)ws_s, (const int64_t*)ws_id, (const double*)ws_b, (const int64_t*)ws_bid,
                      out_score, out_id, out_best, out_best_id);
   HQ_CHECK_LAUNCH();
@@ -6181,8 +6163,7 @@ int hq_select_topk(const double* scores, int Q, int64_t N, int k, double thresho
   if (Q < 0 || N < 0 || k <= 0) return fail(HQ_E_INVALID, "bad shape");
   if (Q == 0) return HQ_OK;
   if (!out_score || !out_id || (N > 0 && !scores)) return fail(HQ_E_INVALID, "null buffer");
-  int grid = Q < 4096 ? Q : 4096;
-  hipLaunchKernelGGL(k_select, dim3(grid), dim3(64), 0, (hipStream_t)stream, scores, Q, N, k, threshold, thr_mode,
+  hipLaunchKernelGGL(k_select, dim3(query_grid(Q, 4096)), dim3(64), 0, (hipStream_t)stream, scores, Q, N, k, threshold, thr_mode,
                      id_base, out_score, out_id, out_best, out_best_id);
   HQ_CHECK_LAUNCH();
   return HQ_OK;
@@ -6197,10 +6178,8 @@ int hq_pair_scores_raw_src(const double* q, const double* C, int64_t N, int m, i
   if (N < 0 || m <= 0) return fail(HQ_E_INVALID, "bad shape");
   if (N == 0) return HQ_OK;
   if (!q || !C || !out) return fail(HQ_E_INVALID, "null buffer");
-  int64_t blocks = (N + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(k_pair_raw, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, q, C, N, m, q_f32 ? 1 : 0,
-                     c_f32 ? 1 : 0, out);
+  hipLaunchKernelGGL(k_pair_raw, dim3(grid_for(N, 256, 8192)), dim3(256), 0, (hipStream_t)stream, q, C, N, m,
+                     q_f32 ? 1 : 0, c_f32 ? 1 : 0, out);
   HQ_CHECK_LAUNCH();
   return HQ_OK;
 }
@@ -6209,10 +6188,8 @@ int hq_cosine_scores(const float* a, int Q, const float* b, int64_t N, int K, do
   if (Q < 0 || N < 0 || K < 0) return fail(HQ_E_INVALID, "bad shape");
   if (Q == 0 || N == 0) return HQ_OK;
   if ((K > 0 && (!a || !b)) || !out) return fail(HQ_E_INVALID, "null buffer");  // K = 0: rows are never read
-  const int64_t total = (int64_t)Q * N;
-  int64_t blocks = (total + 255) / 256;
-  if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(k_cosine, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, a, Q, b, N, K, out);
+  hipLaunchKernelGGL(k_cosine, dim3(grid_for((int64_t)Q * N, 256, 16384)), dim3(256), 0, (hipStream_t)stream, a, Q, b,
+                     N, K, out);
   HQ_CHECK_LAUNCH();
   return HQ_OK;
 }
@@ -6238,10 +6215,8 @@ int hq_seg_packov_split(const double* Z, const double* S, int64_t N, int L, void
   if (!ov_layout(L, o)) return fail(HQ_E_UNSUPPORTED, "no split overall layout for L=%d", L);
   SegInfo si;
   seg_info(L, si);
-  int64_t blocks = (z16_rows(N) * o.nkb * 32 + 255) / 256;
-  if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(k_packov, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, Z, S, N, si.Lp, o,
-                     reinterpret_cast<_Float16*>(Zo16), So32);
+  hipLaunchKernelGGL(k_packov, dim3(grid_for(z16_rows(N) * o.nkb * 32, 256, 16384)), dim3(256), 0, (hipStream_t)stream,
+                     Z, S, N, si.Lp, o, reinterpret_cast<_Float16*>(Zo16), So32);
   HQ_CHECK_LAUNCH();
   return HQ_OK;
 }
@@ -6252,29 +6227,18 @@ int hq_seg_append(const double* idx, int64_t M, int L, int src_f32, const uint8_
   if (L > 4096) return fail(HQ_E_UNSUPPORTED, "L=%d (<= 4096)", L);
   if (M == 0) return HQ_OK;
   if (!idx || !Z || !stats) return fail(HQ_E_INVALID, "null buffer");
-  if ((Z16 == nullptr) != (S32 == nullptr) || (Zov16 == nullptr) != (Sov32 == nullptr))
-    return fail(HQ_E_INVALID, "a split copy needs both of its buffers");
-  if (flags && !S32) return fail(HQ_E_INVALID, "the flagged-row list needs the level-0 copies");
+  const SplitCopies c = split_copies(Z16, S32, Zov16, Sov32, flags);
+  if (int rc = split_copies_paired(c)) return rc;
   if (N0 + M >= 0x7FFFFFFF) return fail(HQ_E_UNSUPPORTED, "N=%lld rows (int32 row ids)", (long long)(N0 + M));
   SegInfo si;
-  seg_info(L, si);
-  if (si.nseg == 0) return fail(HQ_E_INVALID, "no level structure for L=%d", L);
-  if (Z16 && si.plen[0] > 32) return fail(HQ_E_INVALID, "level-0 copies with a level-0 segment of %d values", si.plen[0]);
-  OvLayout o = {};
-  if (Zov16 && !ov_layout(L, o)) return fail(HQ_E_INVALID, "overall copies without a split overall layout (L=%d)", L);
+  OvLayout o;
+  if (int rc = split_copies_check(L, c, si, o)) return rc;
   hipStream_t s = (hipStream_t)stream;
   if (flags && N0 == 0) HQ_CHECK_HIP(hipMemsetAsync(flags, 0, sizeof(int), s));  // an empty corpus lists no rows
-  const int64_t blocks = z16_rows(N0 + M) - N0;  // the new rows, then the pad rows
-  const dim3 grid((unsigned)(blocks < 65536 ? blocks : 65536));
-  if (seg_small(si) && si.nseg <= 8 && opt(OPT_PREP_COOP, 1) != 0) {
-    hipLaunchKernelGGL(k_seg_append<true>, grid, dim3(64), (size_t)8 * si.L, s, idx, M, N0, si, src_f32 ? 1 : 0, row_f32,
-                       Z, stats, reinterpret_cast<_Float16*>(Z16), S32, o, reinterpret_cast<_Float16*>(Zov16), Sov32,
-                       flags);
-  } else {
-    hipLaunchKernelGGL(k_seg_append<false>, grid, dim3(64), (size_t)8 * si.L, s, idx, M, N0, si, src_f32 ? 1 : 0, row_f32,
-                       Z, stats, reinterpret_cast<_Float16*>(Z16), S32, o, reinterpret_cast<_Float16*>(Zov16), Sov32,
-                       flags);
-  }
+  // one workgroup per new row, then per pad row
+  auto kern = prep_coop(si) ? k_seg_append<true> : k_seg_append<false>;
+  hipLaunchKernelGGL(kern, dim3(grid_for(z16_rows(N0 + M) - N0, 1, 65536)), dim3(64), (size_t)8 * si.L, s, idx, M, N0,
+                     si, src_f32 ? 1 : 0, row_f32, Z, stats, c.Z16, c.S32, o, c.Zov16, c.Sov32, c.flags);
   HQ_CHECK_LAUNCH();
   return HQ_OK;
 }
@@ -6287,15 +6251,11 @@ int hq_seg_gather(const int64_t* src_row, int64_t M, int64_t N_src, int L, const
   if (M >= 0x7FFFFFFF) return fail(HQ_E_UNSUPPORTED, "M=%lld rows (int32 row ids)", (long long)M);
   if (M > 0 && (!src_row || !Z_src || !S_src || !Z || !stats)) return fail(HQ_E_INVALID, "null buffer");
   if ((R_src == nullptr) != (R == nullptr)) return fail(HQ_E_INVALID, "the raw rows need both of their buffers");
-  if ((Z16 == nullptr) != (S32 == nullptr) || (Zov16 == nullptr) != (Sov32 == nullptr))
-    return fail(HQ_E_INVALID, "a split copy needs both of its buffers");
-  if (flags && !S32) return fail(HQ_E_INVALID, "the flagged-row list needs the level-0 copies");
+  const SplitCopies c = split_copies(Z16, S32, Zov16, Sov32, flags);
+  if (int rc = split_copies_paired(c)) return rc;
   SegInfo si;
-  seg_info(L, si);
-  if (si.nseg == 0) return fail(HQ_E_INVALID, "no level structure for L=%d", L);
-  if (Z16 && si.plen[0] > 32) return fail(HQ_E_INVALID, "level-0 copies with a level-0 segment of %d values", si.plen[0]);
-  OvLayout o = {};
-  if (Zov16 && !ov_layout(L, o)) return fail(HQ_E_INVALID, "overall copies without a split overall layout (L=%d)", L);
+  OvLayout o;
+  if (int rc = split_copies_check(L, c, si, o)) return rc;
   if ((R && R == R_src) || (Z && Z == Z_src) || (stats && stats == S_src))
     return fail(HQ_E_INVALID, "a destination buffer is its source");
   hipStream_t s = (hipStream_t)stream;
@@ -6304,9 +6264,8 @@ int hq_seg_gather(const int64_t* src_row, int64_t M, int64_t N_src, int L, const
   const int64_t groups = ((Z16 || Zov16) ? z16_rows(M) : M + 3) / 4;
   if (groups == 0) return HQ_OK;
   // one wave per group, dispatched by the hardware (a grid-stride loop only past 2^22 groups)
-  hipLaunchKernelGGL(k_seg_gather, dim3((unsigned)(groups < (1 << 22) ? groups : (1 << 22))), dim3(64), 0, s, src_row,
-                     M, N_src, si, R_src, Z_src, S_src, R, Z, stats, reinterpret_cast<_Float16*>(Z16), S32, o,
-                     reinterpret_cast<_Float16*>(Zov16), Sov32, flags, groups);
+  hipLaunchKernelGGL(k_seg_gather, dim3(grid_for(groups, 1, 1 << 22)), dim3(64), 0, s, src_row, M, N_src, si, R_src,
+                     Z_src, S_src, R, Z, stats, c.Z16, c.S32, o, c.Zov16, c.Sov32, c.flags, groups);
   HQ_CHECK_LAUNCH();
   return HQ_OK;
 }
@@ -6318,34 +6277,19 @@ int hq_seg_replace(const double* idx, int64_t M, const int64_t* rows, int L, int
   if (L > 4096) return fail(HQ_E_UNSUPPORTED, "L=%d (<= 4096)", L);
   if (M == 0) return HQ_OK;
   if (!idx || !rows || !Z || !stats) return fail(HQ_E_INVALID, "null buffer");
-  if ((Z16 == nullptr) != (S32 == nullptr) || (Zov16 == nullptr) != (Sov32 == nullptr))
-    return fail(HQ_E_INVALID, "a split copy needs both of its buffers");
-  if (flags && !S32) return fail(HQ_E_INVALID, "the flagged-row list needs the level-0 copies");
+  const SplitCopies c = split_copies(Z16, S32, Zov16, Sov32, flags);
+  if (int rc = split_copies_paired(c)) return rc;
   if (N >= 0x7FFFFFFF) return fail(HQ_E_UNSUPPORTED, "N=%lld rows (int32 row ids)", (long long)N);
   SegInfo si;
-  seg_info(L, si);
-  if (si.nseg == 0) return fail(HQ_E_INVALID, "no level structure for L=%d", L);
-  if (Z16 && si.plen[0] > 32) return fail(HQ_E_INVALID, "level-0 copies with a level-0 segment of %d values", si.plen[0]);
-  OvLayout o = {};
-  if (Zov16 && !ov_layout(L, o)) return fail(HQ_E_INVALID, "overall copies without a split overall layout (L=%d)", L);
+  OvLayout o;
+  if (int rc = split_copies_check(L, c, si, o)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  const dim3 grid((unsigned)(M < 65536 ? M : 65536));
-  if (seg_small(si) && si.nseg <= 8 && opt(OPT_PREP_COOP, 1) != 0) {
-    hipLaunchKernelGGL(k_seg_replace<true>, grid, dim3(64), (size_t)8 * si.L, s, idx, M, rows, N, si, src_f32 ? 1 : 0,
-                       row_f32, Z, stats, reinterpret_cast<_Float16*>(Z16), S32, o, reinterpret_cast<_Float16*>(Zov16),
-                       Sov32);
-  } else {
-    hipLaunchKernelGGL(k_seg_replace<false>, grid, dim3(64), (size_t)8 * si.L, s, idx, M, rows, N, si, src_f32 ? 1 : 0,
-                       row_f32, Z, stats, reinterpret_cast<_Float16*>(Z16), S32, o, reinterpret_cast<_Float16*>(Zov16),
-                       Sov32);
-  }
+  auto kern = prep_coop(si) ? k_seg_replace<true> : k_seg_replace<false>;
+  hipLaunchKernelGGL(kern, dim3(grid_for(M, 1, 65536)), dim3(64), (size_t)8 * si.L, s, idx, M, rows, N, si,
+                     src_f32 ? 1 : 0, row_f32, Z, stats, c.Z16, c.S32, o, c.Zov16, c.Sov32);
   HQ_CHECK_LAUNCH();
-  if (flags) {  // a replaced row may enter or leave the list: listed again from the N rows' flag words
-    HQ_CHECK_HIP(hipMemsetAsync(flags, 0, sizeof(int), s));
-    const int64_t fb = (N + 255) / 256;
-    hipLaunchKernelGGL(k_flag_rows, dim3((unsigned)(fb < 4096 ? fb : 4096)), dim3(256), 0, s, S32, N, flags + 1, flags);
-    HQ_CHECK_LAUNCH();
-  }
+  // a replaced row may enter or leave the list: listed again from the N rows' flag words
+  if (flags) return hq_seg_flag_rows(S32, N, flags, stream);
   return HQ_OK;
 }
 

@@ -22,6 +22,7 @@ from .. import kernels as K
 from .._dev import is_tensor, to_dev, to_np, torch
 from ..models import QuantizedModel, SearchResult
 from .._compat import bases as _bases
+from .._resident import ResidentRows
 
 MAX_FUSED_K = 64     # list length of the f64 scans (hq_scan_topk)
 MAX_SPLIT_K = 1024   # list length of the split-f16 scans (k > 64: LDS-sorted pools, tiled re-rank)
@@ -135,7 +136,7 @@ class PendingSearch:
         self.counted = False  # in the corpus's count of unfinished batches (IndexCorpus.append's writer rule)
 
 
-class IndexCorpus:
+class IndexCorpus(ResidentRows):
     """A corpus of equal-length hierarchical index vectors resident in HBM.
 
     `indices`: [N, L] (NumPy or device tensor); `id_base`: global id of row 0 (corpus shards).
@@ -185,19 +186,13 @@ class IndexCorpus:
         self._mark_ready()
         self._warm_redo(x)
 
-    def _mark_ready(self):
-        self._built_on = K.stream()
-        self._ready = torch().cuda.Event()
-        self._ready.record()
-
     def _writer(self, what: str):
         """Entry of a writer (append / reserve): no submitted batch unfinished; ordered after the last writer."""
         with _lock(self):
             if self._pending:
                 raise RuntimeError(f"IndexCorpus.{what} with {self._pending} submitted search batch(es) unfinished: "
                                    "call progressive_finish first")
-        if K.stream() != self._built_on:
-            torch().cuda.current_stream().wait_event(self._ready)
+        self._wait_ready()
 
     def reserve(self, capacity: int) -> int:
         """Room for `capacity` rows without another reallocation (device-to-device copies of the resident
@@ -243,19 +238,6 @@ class IndexCorpus:
         self._mark_ready()
         return self.N
 
-    def _local_rows(self, rows, what: str) -> np.ndarray:
-        """Local row numbers (sequence, NumPy array or device tensor) as a host int64 array, every one in
-        [0, N): IndexError otherwise (raised on the host, before any launch)."""
-        a = to_np(rows) if is_tensor(rows) else np.asarray(rows)
-        a = a.reshape(-1)
-        if a.size and a.dtype.kind not in "iu":
-            raise TypeError(f"IndexCorpus.{what}: row numbers must be integers")
-        a = a.astype(np.int64)
-        if a.size and (a.min() < 0 or a.max() >= self.N):
-            bad = int(a.min()) if a.min() < 0 else int(a.max())
-            raise IndexError(f"IndexCorpus.{what}: row {bad} outside [0, {self.N})")
-        return a
-
     def remove(self, rows) -> int:
         """Drop the local rows `rows` (sequence, NumPy array or device tensor; duplicates tolerated).  The
         survivors keep their order and are renumbered consecutively (global id = id_base + new position), exactly
@@ -263,10 +245,7 @@ class IndexCorpus:
         same capacity.  IndexError for a row outside [0, N) and ValueError for removing every row, both before
         any launch.  Statistics and adaptive list lengths are kept.  A writer: see the class docstring.
         Returns the new N."""
-        drop = self._local_rows(rows, "remove")
-        keep = np.ones(self.N, dtype=bool)
-        keep[drop] = False
-        sel = np.flatnonzero(keep)
+        sel = self._survivors(self._local_rows(rows, "remove"))
         if sel.size == 0:
             raise ValueError("IndexCorpus.remove: no row would be left")
         self._writer("remove")
@@ -329,8 +308,7 @@ class IndexCorpus:
         has the global id id_base + i): one hq_seg_gather launch, exactly IndexCorpus(rows' vectors, id_base).
         This corpus is only read (a search, not a writer).  IndexError for a row outside [0, N)."""
         sel = self._local_rows(rows, "select")
-        if K.stream() != self._built_on:
-            torch().cuda.current_stream().wait_event(self._ready)
+        self._wait_ready()
         prep = K.seg_gather(self.prep, sel, cap=max(1, sel.size), checked=True)
         c = object.__new__(IndexCorpus)
         c.N, c.L, c.id_base = prep.N, self.L, int(id_base)
@@ -365,8 +343,7 @@ class IndexCorpus:
         """queries: [Q, L] (or [L]); a pair (array, per-row float32 flags) for mixed-dtype batches."""
         if isinstance(queries, tuple):
             queries, row_f32 = queries
-        if K.stream() != self._built_on:
-            torch().cuda.current_stream().wait_event(self._ready)
+        self._wait_ready()
         f32 = _is_f32(queries)
         q = _f64(queries)
         if q.dim() == 1:

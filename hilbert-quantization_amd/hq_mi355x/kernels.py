@@ -377,6 +377,14 @@ def seg_prepare(idx, exc=None, src_f32: bool = False, row_f32=None) -> Prepared:
 PAD0 = 48  # pad rows of the level-0 copies (hq_mi355x.h: hq_seg_pack0_split)
 
 
+def _rows16(n: int) -> int:
+    return (n + 15) // 16 * 16 + PAD0
+
+
+def _rows4(n: int) -> int:
+    return (n + 3) // 4 * 4 + PAD0
+
+
 @functools.lru_cache(maxsize=None)
 def packov_info(L: int):
     """(K-blocks, G segments, one-value segments, floats per 4-row statistics group) of the split
@@ -387,17 +395,29 @@ def packov_info(L: int):
     return tuple(x.value for x in v)
 
 
+def _alloc_split(p: Prepared, cap: int, level0: bool = False, overall: bool = False, flags: bool = False) -> Prepared:
+    """Give p uninitialised split layouts sized for cap rows: the level-0 copies (Z16, S32), the overall copies
+    (Zov16, Sov32; L must have a split overall layout) and the flagged-row list (F0), each where asked."""
+    t = torch()
+    dev = p.Z.device
+    if level0:
+        p.Z16 = t.empty((_rows16(cap), 64), dtype=t.float16, device=dev)  # tiled rows
+        p.S32 = t.empty((_rows4(cap), 4), dtype=t.float32, device=dev)  # SoA groups of 4 rows
+    if overall:
+        nkb, _, _, gs = packov_info(p.L)
+        p.Zov16 = t.empty((_rows16(cap), nkb * 64), dtype=t.float16, device=dev)  # tiled: 16-row tiles of nkb x 2 KiB
+        p.Sov32 = t.empty((_rows4(cap) // 4, gs), dtype=t.float32, device=dev)  # SoA groups of 4 rows
+    if flags:
+        p.F0 = t.empty(1 + cap, dtype=t.int32, device=dev)  # the count, then the listed rows
+    return p
+
+
 def packov(p: Prepared, exc=None) -> Prepared:
     """Attach the split-f16 copies of every level segment (hq_seg_packov_split) used by the overall
     (brute-force) scan; level structures without a split layout keep the f64 scan."""
-    t = torch()
-    info = packov_info(p.L)
-    if info is None:
+    if packov_info(p.L) is None:
         return p
-    nkb, _, _, gs = info
-    rows = (p.N + 15) // 16 * 16 + PAD0
-    p.Zov16 = t.empty((rows, nkb * 64), dtype=t.float16, device=p.Z.device)  # tiled: 16-row tiles of nkb x 2 KiB
-    p.Sov32 = t.empty(((p.N + 3) // 4 + PAD0 // 4, gs), dtype=t.float32, device=p.Z.device)  # SoA groups of 4 rows
+    _alloc_split(p, p.N, overall=True)
     _chk(_L().hq_seg_packov_split(ptr(p.Z), ptr(p.S), p.N, p.L, ptr(p.Zov16), ptr(p.Sov32), stream()), exc)
     return p
 
@@ -405,11 +425,9 @@ def packov(p: Prepared, exc=None) -> Prepared:
 def pack0(p: Prepared, exc=None) -> Prepared:
     """Attach the split-f16 level-0 copies (hq_seg_pack0_split) used by the level-0 scan; indexes whose
     level-0 segment is longer than 32 values keep the f64 scan."""
-    t = torch()
     if seg_level0_len(p.L) > 32:
         return p
-    p.Z16 = t.empty(((p.N + 15) // 16 * 16 + PAD0, 64), dtype=t.float16, device=p.Z.device)  # tiled rows
-    p.S32 = t.empty(((p.N + 3) // 4 * 4 + PAD0, 4), dtype=t.float32, device=p.Z.device)  # SoA groups of 4 rows
+    _alloc_split(p, p.N, level0=True)
     _chk(_L().hq_seg_pack0_split(ptr(p.Z), ptr(p.S), p.N, p.L, ptr(p.Z16), ptr(p.S32), stream()), exc)
     return p
 
@@ -426,9 +444,7 @@ def seg_prepare_pack0(idx, exc=None, src_f32: bool = False, row_f32=None) -> Pre
     Z = t.empty((N, Lp), dtype=t.float64, device=i2.device)
     S = t.empty((N, ns, 4), dtype=t.float64, device=i2.device)
     rf, any32, all32 = _row_flags(src_f32, row_f32, N, i2.device)
-    p = Prepared(i2, Z, S, L, any32, all32)
-    p.Z16 = t.empty(((N + 15) // 16 * 16 + PAD0, 64), dtype=t.float16, device=i2.device)
-    p.S32 = t.empty(((N + 3) // 4 * 4 + PAD0, 4), dtype=t.float32, device=i2.device)
+    p = _alloc_split(Prepared(i2, Z, S, L, any32, all32), N, level0=True)
     _chk(_L().hq_seg_prepare_pack0(ptr(i2), N, L, 1 if src_f32 else 0, ptr(rf), ptr(Z), ptr(S), ptr(p.Z16),
                                    ptr(p.S32), stream()), exc)
     return p
@@ -439,18 +455,16 @@ def flag_rows(p: Prepared, exc=None) -> Prepared:
     level-0 scan of every query batch skips that pass over the statistics."""
     if p.S32 is None:
         return p
-    t = torch()
-    p.F0 = t.empty(1 + p.N, dtype=t.int32, device=p.Z.device)
+    _alloc_split(p, p.N, flags=True)
     _chk(_L().hq_seg_flag_rows(ptr(p.S32), p.N, ptr(p.F0), stream()), exc)
     return p
 
 
-def _rows16(n: int) -> int:
-    return (n + 15) // 16 * 16 + PAD0
-
-
-def _rows4(n: int) -> int:
-    return (n + 3) // 4 * 4 + PAD0
+def _carry(q: Prepared, p: Prepared) -> Prepared:
+    """q, a new view of p's rows, takes over p's capacity buffers and split layouts."""
+    q.cap, q.base = p.cap, p.base
+    q.Z16, q.S32, q.Zov16, q.Sov32, q.F0 = p.Z16, p.S32, p.Zov16, p.Sov32, p.F0
+    return q
 
 
 def seg_reserve(p: Prepared, capacity: int) -> Prepared:
@@ -471,18 +485,14 @@ def seg_reserve(p: Prepared, capacity: int) -> Prepared:
     Sb[:N].copy_(p.S)
     q = Prepared(Rb[:N], Zb[:N], Sb[:N], p.L, p.f32, p.all32)
     q.cap, q.base = cap, (Rb, Zb, Sb)
+    _alloc_split(q, cap, p.Z16 is not None, p.Zov16 is not None, p.F0 is not None)
     if p.Z16 is not None:
-        q.Z16 = t.empty((_rows16(cap), 64), dtype=t.float16, device=dev)
-        q.S32 = t.empty((_rows4(cap), 4), dtype=t.float32, device=dev)
         q.Z16[:_rows16(N)].copy_(p.Z16[:_rows16(N)])
         q.S32[:_rows4(N)].copy_(p.S32[:_rows4(N)])
     if p.Zov16 is not None:
-        q.Zov16 = t.empty((_rows16(cap), p.Zov16.shape[1]), dtype=t.float16, device=dev)
-        q.Sov32 = t.empty((_rows4(cap) // 4, p.Sov32.shape[1]), dtype=t.float32, device=dev)
         q.Zov16[:_rows16(N)].copy_(p.Zov16[:_rows16(N)])
         q.Sov32[:_rows4(N) // 4].copy_(p.Sov32[:_rows4(N) // 4])
     if p.F0 is not None:
-        q.F0 = t.empty(1 + cap, dtype=t.int32, device=dev)
         q.F0[:1 + N].copy_(p.F0[:1 + N])  # the count and (at most N) listed rows
     return q
 
@@ -508,10 +518,7 @@ def seg_append(p: Prepared, rows, src_f32: bool = False, row_f32=None, exc=None)
     Rb[N0:N1].copy_(r2)
     _chk(_L().hq_seg_append(ptr(r2), M, L, 1 if src_f32 else 0, ptr(rf), N0, ptr(Zb), ptr(Sb), ptr(p.Z16), ptr(p.S32),
                             ptr(p.Zov16), ptr(p.Sov32), ptr(p.F0), stream()), exc)
-    q = Prepared(Rb[:N1], Zb[:N1], Sb[:N1], L, p.f32 or any32, all32 and (p.all32 or N0 == 0))
-    q.cap, q.base = p.cap, p.base
-    q.Z16, q.S32, q.Zov16, q.Sov32, q.F0 = p.Z16, p.S32, p.Zov16, p.Sov32, p.F0
-    return q
+    return _carry(Prepared(Rb[:N1], Zb[:N1], Sb[:N1], L, p.f32 or any32, all32 and (p.all32 or N0 == 0)), p)
 
 
 def _row_ids(rows, n: int, dev, what: str, checked: bool = False):
@@ -566,14 +573,7 @@ def seg_gather(p: Prepared, src_rows, cap: Optional[int] = None, exc=None, check
     Sb = t.empty((cap, p.nseg, 4), dtype=t.float64, device=dev)
     q = Prepared(Rb[:M], Zb[:M], Sb[:M], p.L)
     q.cap, q.base = cap, (Rb, Zb, Sb)
-    if p.Z16 is not None:
-        q.Z16 = t.empty((_rows16(cap), 64), dtype=t.float16, device=dev)
-        q.S32 = t.empty((_rows4(cap), 4), dtype=t.float32, device=dev)
-    if p.Zov16 is not None:
-        q.Zov16 = t.empty((_rows16(cap), p.Zov16.shape[1]), dtype=t.float16, device=dev)
-        q.Sov32 = t.empty((_rows4(cap) // 4, p.Sov32.shape[1]), dtype=t.float32, device=dev)
-    if p.F0 is not None:
-        q.F0 = t.empty(1 + cap, dtype=t.int32, device=dev)
+    _alloc_split(q, cap, p.Z16 is not None, p.Zov16 is not None, p.F0 is not None)
     _chk(_L().hq_seg_gather(ptr(sel), M, p.N, p.L, ptr(p.R), ptr(p.Z), ptr(p.S), ptr(Rb), ptr(Zb), ptr(Sb), ptr(q.Z16),
                             ptr(q.S32), ptr(q.Zov16), ptr(q.Sov32), ptr(q.F0), stream()), exc)
     q.f32, q.all32 = _f32_state(p, q.S)
@@ -606,9 +606,7 @@ def seg_replace(p: Prepared, rows, new_rows, src_f32: bool = False, row_f32=None
     p.R.index_copy_(0, sel, r2)
     _chk(_L().hq_seg_replace(ptr(r2), M, ptr(sel), L, 1 if src_f32 else 0, ptr(rf), p.N, ptr(p.Z), ptr(p.S), ptr(p.Z16),
                              ptr(p.S32), ptr(p.Zov16), ptr(p.Sov32), ptr(p.F0), stream()), exc)
-    q = Prepared(p.R, p.Z, p.S, L, p.f32 or any32, all32 and p.all32)
-    q.cap, q.base = p.cap, p.base
-    q.Z16, q.S32, q.Zov16, q.Sov32, q.F0 = p.Z16, p.S32, p.Zov16, p.Sov32, p.F0
+    q = _carry(Prepared(p.R, p.Z, p.S, L, p.f32 or any32, all32 and p.all32), p)
     if q.f32 and not q.all32:  # mixed: float32 rows may all have left, or every float64 row may have
         q.f32, q.all32 = _f32_state(q, q.S)
     return q
@@ -698,40 +696,49 @@ def scan_topk(q: Prepared, c: Prepared, mode: int, k: int, threshold: float = 0.
     return sc, ids, best, bid
 
 
+def _refine_outputs(cand_id, k: int, lists: bool = True):
+    """The re-rank outputs of the lists cand_id [Q, kp]: (scores [Q, k], ids [Q, k], count [Q], resolved [Q]);
+    lists False: no scores and ids (None)."""
+    t = torch()
+    Q, dev = cand_id.shape[0], cand_id.device
+    os_ = t.empty((Q, k), dtype=t.float64, device=dev) if lists else None
+    oi = t.empty((Q, k), dtype=t.int64, device=dev) if lists else None
+    return os_, oi, t.empty(Q, dtype=t.int32, device=dev), t.empty(Q, dtype=t.int32, device=dev)
+
+
+def _refine_args(q, c, mode, cand_score, cand_id, k, threshold, thr_mode, eps, id_base, outs):
+    """The leading arguments the hq_refine_* entries share: both vector sets, (mode; None: hq_refine_final_ws,
+    which takes none,) the lists, their sizes and threshold, the four outputs."""
+    Q, kp = cand_id.shape
+    return (ptr(q.R), ptr(q.Z), ptr(q.S), Q, ptr(c.R), ptr(c.Z), ptr(c.S), c.N, c.L, *(() if mode is None else (mode,)),
+            ptr(_contig(cand_score)), ptr(_contig(cand_id)), kp, k, float(threshold), thr_mode, float(eps), int(id_base),
+            *(ptr(o) for o in outs))
+
+
 def refine_topk(q: Prepared, c: Prepared, mode: int, cand_score, cand_id, k: int, threshold: float = 0.0,
                 thr_mode: int = 0, eps: float = 1e-9, id_base: int = 0, exc=None, redo=None, count_empty: bool = False):
     """Exact re-rank of a scan list -> (scores [Q, k], ids [Q, k], count [Q], resolved [Q]).  redo (device
     int32 [1], optional): set to the number of queries needing the dense path (unresolved, or with
     count_empty, nothing passed)."""
-    t = torch()
-    Q, kp = cand_id.shape
-    dev = cand_id.device
-    os_ = t.empty((Q, k), dtype=t.float64, device=dev)
-    oi = t.empty((Q, k), dtype=t.int64, device=dev)
-    cnt = t.empty(Q, dtype=t.int32, device=dev)
-    res = t.empty(Q, dtype=t.int32, device=dev)
+    kp = cand_id.shape[1]
+    outs = _refine_outputs(cand_id, k)
     if kp > 64:  # long lists: the lane-cooperative re-rank with its workspace
-        _refine_ws(q, c, mode, cand_score, cand_id, kp, k, threshold, thr_mode, eps, id_base, os_, oi, cnt, res,
-                   count_empty, redo, None, None, exc)
-        return os_, oi, cnt, res
-    _chk(_L().hq_refine_topk(ptr(q.R), ptr(q.Z), ptr(q.S), Q, ptr(c.R), ptr(c.Z), ptr(c.S), c.N, c.L, mode,
-                             ptr(_contig(cand_score)), ptr(_contig(cand_id)), kp, k, float(threshold), thr_mode,
-                             float(eps), int(id_base), ptr(os_), ptr(oi), ptr(cnt), ptr(res), 1 if count_empty else 0,
-                             ptr(redo), stream()), exc)
-    return os_, oi, cnt, res
+        _refine_ws(q, c, mode, cand_score, cand_id, kp, k, threshold, thr_mode, eps, id_base, *outs, count_empty, redo,
+                   None, None, exc)
+        return outs
+    _chk(_L().hq_refine_topk(*_refine_args(q, c, mode, cand_score, cand_id, k, threshold, thr_mode, eps, id_base, outs),
+                             1 if count_empty else 0, ptr(redo), stream()), exc)
+    return outs
 
 
 def _refine_ws(q, c, mode, cand_score, cand_id, kp, k, threshold, thr_mode, eps, id_base, os_, oi, cnt, res,
                count_empty, redo, next_redo, det, exc):
     """hq_refine_topk_ws (lists > 64: k_rank_pairs + k_rank_sort) on the stream's reusable workspace (the
     scan that produced the list has finished with it in stream order)."""
-    Q = int(cand_id.shape[0])
-    dev = cand_id.device
-    wb = int(_lib.load().hq_refine_workspace_size(Q, kp, c.L))
-    ws = _workspace(wb, dev)
-    _chk(_L().hq_refine_topk_ws(ptr(q.R), ptr(q.Z), ptr(q.S), Q, ptr(c.R), ptr(c.Z), ptr(c.S), c.N, c.L, mode,
-                                ptr(_contig(cand_score)), ptr(_contig(cand_id)), kp, k, float(threshold), thr_mode,
-                                float(eps), int(id_base), ptr(os_), ptr(oi), ptr(cnt), ptr(res),
+    wb = int(_lib.load().hq_refine_workspace_size(int(cand_id.shape[0]), kp, c.L))
+    ws = _workspace(wb, cand_id.device)
+    _chk(_L().hq_refine_topk_ws(*_refine_args(q, c, mode, cand_score, cand_id, k, threshold, thr_mode, eps, id_base,
+                                              (os_, oi, cnt, res)),
                                 1 if count_empty else 0, ptr(redo), ptr(next_redo), ptr(det), ptr(ws), wb, stream()),
          exc)
 
@@ -758,10 +765,7 @@ def refine_final_ws(q: Prepared, c: Prepared, cand_score, cand_id, k: int, thres
         return None
     _chk(rc, exc)
     # the level-0 lists are not returned (FINAL_LEVEL0_LISTS False: not written)
-    os_ = t.empty((Q, k), dtype=t.float64, device=dev) if FINAL_LEVEL0_LISTS else None
-    oi = t.empty((Q, k), dtype=t.int64, device=dev) if FINAL_LEVEL0_LISTS else None
-    cnt = t.empty(Q, dtype=t.int32, device=dev)
-    res = t.empty(Q, dtype=t.int32, device=dev)
+    outs = _refine_outputs(cand_id, k, FINAL_LEVEL0_LISTS)
     fid = t.empty((Q, K_out), dtype=t.int64, device=dev)
     fdet = t.empty((Q, K_out, 1 + q.nseg), dtype=t.float64, device=dev)
     fcnt = t.empty(Q, dtype=t.int32, device=dev)
@@ -769,15 +773,14 @@ def refine_final_ws(q: Prepared, c: Prepared, cand_score, cand_id, k: int, thres
     if kp > 64:  # lists <= 64 take k_rank_small, which needs no workspace
         wb = int(_lib.load().hq_refine_workspace_size(Q, kp, c.L))
         ws = _workspace(wb, dev)
-    rc = _L().hq_refine_final_ws(ptr(q.R), ptr(q.Z), ptr(q.S), Q, ptr(c.R), ptr(c.Z), ptr(c.S), c.N, c.L,
-                                 ptr(_contig(cand_score)), ptr(_contig(cand_id)), kp, k, float(threshold), thr_mode,
-                                 float(eps), int(id_base), ptr(os_), ptr(oi), ptr(cnt), ptr(res), ptr(redo),
-                                 ptr(next_redo), int(K_out), ptr(fid), ptr(fdet), ptr(fcnt), ptr(ws), wb,
+    rc = _L().hq_refine_final_ws(*_refine_args(q, c, None, cand_score, cand_id, k, threshold, thr_mode, eps, id_base,
+                                               outs),
+                                 ptr(redo), ptr(next_redo), int(K_out), ptr(fid), ptr(fdet), ptr(fcnt), ptr(ws), wb,
                                  stream())
     if rc == _lib.HQ_E_UNSUPPORTED:
         return None
     _chk(rc, exc)
-    return cnt, res, fid, fdet, fcnt
+    return outs[2], outs[3], fid, fdet, fcnt
 
 
 def refine_rescore_topk(q: Prepared, c: Prepared, mode: int, cand_score, cand_id, k: int, threshold: float = 0.0,
@@ -787,28 +790,19 @@ def refine_rescore_topk(q: Prepared, c: Prepared, mode: int, cand_score, cand_id
     ids, zeros in empty slots) -> (scores, ids, count, resolved, det [Q, k, 1 + nseg])."""
     t = torch()
     Q, kp = cand_id.shape
-    dev = cand_id.device
-    os_ = t.empty((Q, k), dtype=t.float64, device=dev)
-    oi = t.empty((Q, k), dtype=t.int64, device=dev)
-    cnt = t.empty(Q, dtype=t.int32, device=dev)
-    res = t.empty(Q, dtype=t.int32, device=dev)
-    det = t.empty((Q, k, 1 + q.nseg), dtype=t.float64, device=dev)
+    outs = _refine_outputs(cand_id, k)
+    det = t.empty((Q, k, 1 + q.nseg), dtype=t.float64, device=cand_id.device)
+    ce = 1 if count_empty else 0
     if kp > 64:  # long lists: the lane-cooperative re-rank with its workspace
-        _refine_ws(q, c, mode, cand_score, cand_id, kp, k, threshold, thr_mode, eps, id_base, os_, oi, cnt, res,
-                   count_empty, redo, next_redo, det, exc)
-        return os_, oi, cnt, res, det
+        _refine_ws(q, c, mode, cand_score, cand_id, kp, k, threshold, thr_mode, eps, id_base, *outs, count_empty, redo,
+                   next_redo, det, exc)
+        return (*outs, det)
+    head = _refine_args(q, c, mode, cand_score, cand_id, k, threshold, thr_mode, eps, id_base, outs)
     if next_redo is not None:  # ping-pong counters: redo arrives zeroed, the kernel clears next_redo
-        _chk(_L().hq_refine_rescore_topk_pp(ptr(q.R), ptr(q.Z), ptr(q.S), Q, ptr(c.R), ptr(c.Z), ptr(c.S), c.N, c.L,
-                                            mode, ptr(_contig(cand_score)), ptr(_contig(cand_id)), kp, k,
-                                            float(threshold), thr_mode, float(eps), int(id_base), ptr(os_), ptr(oi),
-                                            ptr(cnt), ptr(res), 1 if count_empty else 0, ptr(redo), ptr(next_redo),
-                                            ptr(det), stream()), exc)
-        return os_, oi, cnt, res, det
-    _chk(_L().hq_refine_rescore_topk(ptr(q.R), ptr(q.Z), ptr(q.S), Q, ptr(c.R), ptr(c.Z), ptr(c.S), c.N, c.L, mode,
-                                     ptr(_contig(cand_score)), ptr(_contig(cand_id)), kp, k, float(threshold),
-                                     thr_mode, float(eps), int(id_base), ptr(os_), ptr(oi), ptr(cnt), ptr(res),
-                                     1 if count_empty else 0, ptr(redo), ptr(det), stream()), exc)
-    return os_, oi, cnt, res, det
+        _chk(_L().hq_refine_rescore_topk_pp(*head, ce, ptr(redo), ptr(next_redo), ptr(det), stream()), exc)
+    else:
+        _chk(_L().hq_refine_rescore_topk(*head, ce, ptr(redo), ptr(det), stream()), exc)
+    return (*outs, det)
 
 
 def rescore(q: Prepared, c: Prepared, ids, id_base: int = 0, exc=None):

@@ -16,6 +16,7 @@ import numpy as np
 from .. import _lib
 from .. import kernels as K
 from .._dev import dtype_code, is_tensor, ptr, stream, to_dev, to_np, torch
+from .._resident import ResidentRows
 
 
 def _score_dtype(*arrays) -> np.dtype:
@@ -86,7 +87,7 @@ class FrameCosineCorpus:
         return K.cosine_topk(K.cos_prepare(q2), self._rows, int(k), thr, mode)
 
 
-class QuantizedFrameCorpus:
+class QuantizedFrameCorpus(ResidentRows):
     """The store's own u8 frames [N, r, c] with their (min, max) pairs [N, 2], prepared once for the exact
     integer cosine (hq_cosq_prepare) and searched without decoding: only the signed bytes (1 B per value, in
     int8 MFMA operand fragments) and four float64 statistics per frame stay resident.
@@ -153,17 +154,6 @@ class QuantizedFrameCorpus:
         c._built_on = c._ready = None
         return c
 
-    # ---- the writer rule ------------------------------------------------------------------------------------
-    def _mark_ready(self):
-        self._built_on = K.stream()
-        self._ready = torch().cuda.Event()
-        self._ready.record()
-
-    def _wait_ready(self):
-        """Entry of every search and writer: ordered after the last writer (an event wait queued on the device)."""
-        if self._ready is not None and K.stream() != self._built_on:
-            torch().cuda.current_stream().wait_event(self._ready)
-
     # ---- host-side checks (before any launch) ----------------------------------------------------------------
     @staticmethod
     def _host_keys(keys, M: int, what: str):
@@ -203,18 +193,6 @@ class QuantizedFrameCorpus:
         if int(np.prod(minmax.shape)) != 2 * shape[0]:
             raise ValueError(f"QuantizedFrameCorpus.{what}: minmax {tuple(minmax.shape)} for {shape[0]} frames")
         return shape[0]
-
-    def _local_rows(self, rows, what: str) -> np.ndarray:
-        """Row numbers (sequence, NumPy array or device tensor) as a host int64 array, every one in [0, N)."""
-        a = to_np(rows) if is_tensor(rows) else np.asarray(rows)
-        a = a.reshape(-1)
-        if a.size and a.dtype.kind not in "iu":
-            raise TypeError(f"QuantizedFrameCorpus.{what}: row numbers must be integers")
-        a = a.astype(np.int64)
-        if a.size and (a.min() < 0 or a.max() >= self.N):
-            bad = int(a.min()) if a.min() < 0 else int(a.max())
-            raise IndexError(f"QuantizedFrameCorpus.{what}: row {bad} outside [0, {self.N})")
-        return a
 
     def _frames3(self, frames_u8):
         x = to_dev(frames_u8)
@@ -287,10 +265,7 @@ class QuantizedFrameCorpus:
         """Drop the positions `rows` (duplicates tolerated).  The survivors keep their order and are renumbered
         consecutively, exactly as a fresh corpus of the surviving frames would be: one hq_cosq_gather launch into
         a second pair of buffers of the same capacity.  A writer.  Returns the new N."""
-        drop = self._local_rows(rows, "remove")
-        keep = np.ones(self.N, dtype=bool)
-        keep[drop] = False
-        sel = np.flatnonzero(keep)
+        sel = self._survivors(self._local_rows(rows, "remove"))
         if sel.size == 0:
             raise ValueError("QuantizedFrameCorpus.remove: no frame would be left")
         if sel.size == self.N:
