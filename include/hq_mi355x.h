@@ -69,9 +69,12 @@ int hq_set_option(const char* name, int64_t value);
 int hq_reset_option(const char* name);
 int hq_get_option(const char* name, int64_t* value);
 int hq_diag_build(void);
-/* DIAG builds: bounds violations counted by the guarded corpus-row loads of the level-0 scan (k_scan0g,
- * k_sample_topg, k_pool_select; the load is clamped instead of faulting) since the library loaded, and
- * the source line of the first.  Synchronises the device.  Default builds report 0.                  */
+/* DIAG builds: bounds violations counted by the guarded row loads of the level-0 scan (k_scan0g,
+ * k_sample_topg, k_pool_select) and of the corpus mutation kernels (k_seg_append, k_seg_gather,
+ * k_seg_replace) since the library loaded (the load is clamped instead of faulting), and where the
+ * first was seen: *first_line = part * 10000 + line, part 0 being csrc/hq_search.hip itself
+ * and part n the file under csrc/search/ that sets HQ_PART n at its top, line the line in that file.
+ * Synchronises the device.  Default builds report 0.                                               */
 int hq_diag_violations(int64_t* count, int* first_line);
 /* Launch geometry of the level-0 scan k_scan0g, exactly as launched (host only): query blocks of 64, corpus chunks (a multiple
  * of 8: XCD map) of chunk_len rows (a multiple of 16), and the row counts of the split copies it reads

@@ -193,12 +193,12 @@ def test_retired_scan_options_are_unknown_and_kept_ones_work(lib):
 
 
 def _scan0g_reads(n_rows: int) -> int:
-    """Rows from its first that one k_scan0g wave reads for a chunk holding n_rows rows (hq_search.hip k_scan0g):
-    nsteps = ceil(n_rows / 16) whole 16-row steps; the prologue loads steps min(u, nsteps - 1), each body loads
-    step min(s + PF, nsteps - 1) (the prefetch index is clamped to the chunk's last step), and the drain reads
-    the statistics of four rows inside a step it has scanned.  Code: hq_search.hip:1297 (nsteps), :1300 and
-    :1304 (the clamped prologue and body loads), :1181 (the drain's statistics group), :1129 (a chunk that
-    starts at or past N exits before any load)."""
+    """Rows from its first that one k_scan0g wave reads for a chunk holding n_rows rows (csrc/hq_search.hip,
+    k_scan0g): nsteps = ceil(n_rows / 16) whole 16-row steps; the prologue loads steps min(u, nsteps - 1), each
+    body loads step min(s + PF, nsteps - 1) (the prefetch index is clamped to the chunk's last step), and the
+    drain reads the statistics of four rows inside a step it has scanned.  Code, all in k_scan0g: `nsteps` and
+    the two clamped `load_step` calls below it (the prologue loop and the one in `body`), the `stt` group load in
+    the `drain` lambda, and the `c_begin >= a.N` return (a chunk that starts at or past N exits before any load)."""
     return 16 * ((n_rows + 15) // 16)
 
 
