@@ -7,6 +7,12 @@
 //                      any pair (different heights, different L, dropped rows, zero blocks and windows, ws < 2).
 //                      One wave per pair, the windows spread over its lanes, the query frame and its window norms
 //                      staged in LDS once per workgroup for the 32 frames the workgroup walks.
+//   hq_comp_scores_listed  the same score through an id list [Q, C]: the frames are read in place, both kernels call
+//                      one per-pair function (comp_pair), so an entry is bit for bit the dense kernel's value.
+//   hq_list_topk       the first k of a scored list by (score desc, list position asc): the engine's stable sort,
+//                      threshold and cut (engine.py:512, 777-781), one workgroup per query.
+//   hq_list_windows    every candidate widened to its window of consecutive frames (frame_cache.py:66-72), first
+//                      appearances in order, one workgroup per query.
 //   hq_comp_prepare    frames of one profile (h, L = H - h, every index row non-zero) -> "composite" rows in
 //                      hq_cos_prepare's tiled split-f16 fragment layout, so that hq_cos_scores_mfma / hq_cos_topk,
 //                      unchanged, return the comprehensive score: for such frames the score is an affine function
@@ -108,6 +114,125 @@ __device__ __forceinline__ double comp_cos01(double dot, double na, double nb) {
   return (na != 0.0 && nb != 0.0) ? (dot / (sqrt(na) * sqrt(nb)) + 1.0) / 2.0 : 0.0;
 }
 
+// One (query, frame) pair by one wave: the staged query frame qf with its descriptor (hq_, Lq, maskq), window geometry
+// gq / nwq and window square norms qn, against frame b (hc clamped by the caller, Lc, maskc).  wsc: the wave's window
+// score list.  Returns the score on every lane; pt[3] = the components.  Shared by k_comp_scores and
+// k_comp_scores_listed, so that both write the same bits for a pair.
+template <typename T>
+__device__ __forceinline__ double comp_pair(const T* qf, int hq_, int Lq, unsigned maskq, const CompWin& gq, int nwq,
+                                            const double* qn, double* wsc, const T* __restrict__ b, int hc, int Lc,
+                                            unsigned maskc, int H, int W, const double* __restrict__ wt, int ML,
+                                            int lane, double* pt) {
+  // hierarchical: the non-zero index rows of each frame in order, zero-padded to M = max(L_q, L_c) levels,
+  // weights of M levels, accumulated left to right (engine.py:535-551, 1053-1099)
+  double hier = 0.0;
+  if (Lq > 0 && Lc > 0) {
+    const int M = Lq > Lc ? Lq : Lc;
+    if (M > ML) {
+      hier = nan("");  // outside the caller's weight table: never read past it
+    } else {
+      const double* w = wt + (size_t)M * ML;
+      unsigned mq = maskq, mc = maskc;
+      double tot = 0.0, tw = 0.0;
+      for (int l = 0; l < M; ++l) {
+        int rq = -1, rc = -1;
+        if (mq) { rq = hq_ + __ffs(mq) - 1; mq &= mq - 1; }
+        if (mc) { rc = hc + __ffs(mc) - 1; mc &= mc - 1; }
+        double s = 0.0;
+        if (rq >= 0 && rc >= 0 && rq < H && rc < H) {
+          double dot = 0.0, na = 0.0, nb = 0.0;
+          for (int c = lane; c < W; c += 64) {
+            const double x = (double)qf[rq * W + c], y = (double)b[rc * W + c];
+            dot = fma(x, y, dot);
+            na = fma(x, x, na);
+            nb = fma(y, y, nb);
+          }
+          s = comp_cos01(wave_sum(dot), wave_sum(na), wave_sum(nb));
+        }
+        tot += s * w[l];
+        tw += w[l];
+      }
+      hier = tw != 0.0 ? tot / tw : 0.0;
+    }
+  }
+  // embedding: the original blocks flattened, truncated to the common length (engine.py:604-660)
+  double emb;
+  {
+    const int m = (hq_ < hc ? hq_ : hc) * W;
+    double dot = 0.0, na = 0.0, nb = 0.0;
+    for (int i = lane; i < m; i += 64) {
+      const double x = (double)qf[i], y = (double)b[i];
+      dot = fma(x, y, dot);
+      na = fma(x, x, na);
+      nb = fma(y, y, nb);
+    }
+    emb = comp_cos01(wave_sum(dot), wave_sum(na), wave_sum(nb));
+  }
+  // spatial (engine.py:662-714): 0.0 for different heights; ws < 2: the embedding cosine
+  double spa = 0.0;
+  if (hq_ == hc) {
+    if (gq.ws < 2) {
+      spa = emb;
+    } else {
+      for (int w = lane; w < nwq; w += 64) {
+        const int off = (w / gq.nj) * gq.st * W + (w % gq.nj) * gq.st;
+        double dot = 0.0, nb = 0.0;
+        for (int r = 0; r < gq.wr; ++r)
+          for (int c = 0; c < gq.wc; ++c) {
+            const double x = (double)qf[off + r * W + c], y = (double)b[off + r * W + c];
+            dot = fma(x, y, dot);
+            nb = fma(y, y, nb);
+          }
+        wsc[w] = comp_cos01(dot, qn[w], nb);
+      }
+      __threadfence_block();
+      __builtin_amdgcn_wave_barrier();
+      double mean = 0.0;
+      if (lane == 0) {
+        auto f = [&](int k) -> double { return wsc[k]; };
+        mean = np_sum<double>(f, nwq) / (double)nwq;
+      }
+      spa = __shfl(mean, 0, 64);
+      __threadfence_block();
+      __builtin_amdgcn_wave_barrier();  // lane 0 has read the list before the next pair rewrites it
+    }
+  }
+  pt[0] = hier;
+  pt[1] = emb;
+  pt[2] = spa;
+  return 0.5 * hier + 0.3 * emb + 0.2 * spa;
+}
+
+// Stage query q for its workgroup: the frame into qf, its window square norms into qn; the clamped height, level
+// count, row mask and window geometry come back by reference.  Every thread of the workgroup calls it.
+template <typename T>
+__device__ __forceinline__ void comp_stage_query(const T* __restrict__ Qi, const int* __restrict__ dq, int q, int H,
+                                                 int W, T* qf, double* qn, int& hq_, int& Lq, unsigned& maskq,
+                                                 CompWin& gq) {
+  const int img = H * W;
+  __syncthreads();  // the previous query's readers are done
+  const T* a = Qi + (int64_t)q * img;
+  for (int i = threadIdx.x; i < img; i += 256) qf[i] = a[i];
+  // heights are clamped to [1, H]: a descriptor this library did not write cannot steer a read outside a frame
+  hq_ = min(max(dq[4 * q], 1), H);
+  Lq = dq[4 * q + 1];
+  maskq = (unsigned)dq[4 * q + 3];
+  gq = comp_windows(hq_, W);
+  const int nwq = gq.count();  // <= nw_cap (the host sizes nw_cap over every height)
+  __syncthreads();
+  for (int w = threadIdx.x; w < nwq; w += 256) {
+    const T* x = qf + (w / gq.nj) * gq.st * W + (w % gq.nj) * gq.st;
+    double na = 0.0;
+    for (int r = 0; r < gq.wr; ++r)
+      for (int c = 0; c < gq.wc; ++c) {
+        const double v = (double)x[r * W + c];
+        na = fma(v, v, na);
+      }
+    qn[w] = na;
+  }
+  __syncthreads();
+}
+
 // LDS: window scores [4 waves][nw_cap] f64, the staged query's window square norms [nw_cap] f64, the query frame
 // [H W] T.  Workgroup (x, y): frames 32 x .. 32 x + 31 against queries y, y + gridDim.y, ...
 template <typename T>
@@ -124,115 +249,156 @@ __global__ __launch_bounds__(256) void k_comp_scores(const T* __restrict__ Qi, c
   const int64_t c0 = (int64_t)blockIdx.x * kCompCand;
   const int64_t c1 = c0 + kCompCand < N ? c0 + kCompCand : N;
   for (int q = blockIdx.y; q < Qn; q += gridDim.y) {
-    __syncthreads();  // the previous query's readers are done
-    const T* a = Qi + (int64_t)q * img;
-    for (int i = threadIdx.x; i < img; i += 256) qf[i] = a[i];
-    // heights are clamped to [1, H]: a descriptor this library did not write cannot steer a read outside a frame
-    const int hq_ = min(max(dq[4 * q], 1), H), Lq = dq[4 * q + 1];
-    const unsigned maskq = (unsigned)dq[4 * q + 3];
-    const CompWin gq = comp_windows(hq_, W);
-    const int nwq = gq.count();  // <= nw_cap (the host sizes nw_cap over every height)
-    __syncthreads();
-    for (int w = threadIdx.x; w < nwq; w += 256) {
-      const T* x = qf + (w / gq.nj) * gq.st * W + (w % gq.nj) * gq.st;
-      double na = 0.0;
-      for (int r = 0; r < gq.wr; ++r)
-        for (int c = 0; c < gq.wc; ++c) {
-          const double v = (double)x[r * W + c];
-          na = fma(v, v, na);
-        }
-      qn[w] = na;
-    }
-    __syncthreads();
+    int hq_, Lq;
+    unsigned maskq;
+    CompWin gq;
+    comp_stage_query(Qi, dq, q, H, W, qf, qn, hq_, Lq, maskq, gq);
     for (int64_t cand = c0 + wv; cand < c1; cand += 4) {
-      const T* b = Ci + cand * img;
-      const int hc = min(max(dc[4 * cand], 1), H), Lc = dc[4 * cand + 1];
-      const unsigned maskc = (unsigned)dc[4 * cand + 3];
-      // hierarchical: the non-zero index rows of each frame in order, zero-padded to M = max(L_q, L_c) levels,
-      // weights of M levels, accumulated left to right (engine.py:535-551, 1053-1099)
-      double hier = 0.0;
-      if (Lq > 0 && Lc > 0) {
-        const int M = Lq > Lc ? Lq : Lc;
-        if (M > ML) {
-          hier = nan("");  // outside the caller's weight table: never read past it
-        } else {
-          const double* w = wt + (size_t)M * ML;
-          unsigned mq = maskq, mc = maskc;
-          double tot = 0.0, tw = 0.0;
-          for (int l = 0; l < M; ++l) {
-            int rq = -1, rc = -1;
-            if (mq) { rq = hq_ + __ffs(mq) - 1; mq &= mq - 1; }
-            if (mc) { rc = hc + __ffs(mc) - 1; mc &= mc - 1; }
-            double s = 0.0;
-            if (rq >= 0 && rc >= 0 && rq < H && rc < H) {
-              double dot = 0.0, na = 0.0, nb = 0.0;
-              for (int c = lane; c < W; c += 64) {
-                const double x = (double)qf[rq * W + c], y = (double)b[rc * W + c];
-                dot = fma(x, y, dot);
-                na = fma(x, x, na);
-                nb = fma(y, y, nb);
-              }
-              s = comp_cos01(wave_sum(dot), wave_sum(na), wave_sum(nb));
-            }
-            tot += s * w[l];
-            tw += w[l];
-          }
-          hier = tw != 0.0 ? tot / tw : 0.0;
-        }
-      }
-      // embedding: the original blocks flattened, truncated to the common length (engine.py:604-660)
-      double emb;
-      {
-        const int m = (hq_ < hc ? hq_ : hc) * W;
-        double dot = 0.0, na = 0.0, nb = 0.0;
-        for (int i = lane; i < m; i += 64) {
-          const double x = (double)qf[i], y = (double)b[i];
-          dot = fma(x, y, dot);
-          na = fma(x, x, na);
-          nb = fma(y, y, nb);
-        }
-        emb = comp_cos01(wave_sum(dot), wave_sum(na), wave_sum(nb));
-      }
-      // spatial (engine.py:662-714): 0.0 for different heights; ws < 2: the embedding cosine
-      double spa = 0.0;
-      if (hq_ == hc) {
-        if (gq.ws < 2) {
-          spa = emb;
-        } else {
-          for (int w = lane; w < nwq; w += 64) {
-            const int off = (w / gq.nj) * gq.st * W + (w % gq.nj) * gq.st;
-            double dot = 0.0, nb = 0.0;
-            for (int r = 0; r < gq.wr; ++r)
-              for (int c = 0; c < gq.wc; ++c) {
-                const double x = (double)qf[off + r * W + c], y = (double)b[off + r * W + c];
-                dot = fma(x, y, dot);
-                nb = fma(y, y, nb);
-              }
-            wsc[w] = comp_cos01(dot, qn[w], nb);
-          }
-          __threadfence_block();
-          __builtin_amdgcn_wave_barrier();
-          double mean = 0.0;
-          if (lane == 0) {
-            auto f = [&](int k) -> double { return wsc[k]; };
-            mean = np_sum<double>(f, nwq) / (double)nwq;
-          }
-          spa = __shfl(mean, 0, 64);
-          __threadfence_block();
-          __builtin_amdgcn_wave_barrier();  // lane 0 has read the list before the next pair rewrites it
-        }
-      }
+      const int hc = min(max(dc[4 * cand], 1), H);
+      double pt[3];
+      const double score = comp_pair(qf, hq_, Lq, maskq, gq, gq.count(), qn, wsc, Ci + cand * img, hc,
+                                     dc[4 * cand + 1], (unsigned)dc[4 * cand + 3], H, W, wt, ML, lane, pt);
       if (lane == 0) {
         const int64_t o = (int64_t)q * N + cand;
-        out[o] = 0.5 * hier + 0.3 * emb + 0.2 * spa;
+        out[o] = score;
         if (parts) {
-          parts[3 * o + 0] = hier;
-          parts[3 * o + 1] = emb;
-          parts[3 * o + 2] = spa;
+          parts[3 * o + 0] = pt[0];
+          parts[3 * o + 1] = pt[1];
+          parts[3 * o + 2] = pt[2];
         }
       }
     }
   }
+}
+
+// The same pairs through an id list: workgroup (x, y) walks entries 32 x .. 32 x + 31 of ids[q] for queries y,
+// y + gridDim.y, ...; the frame of entry j is read in place at Ci + ids[q, j] H W.  An id outside [0, N) is a pad:
+// -inf, parts 0.0, nothing read.
+template <typename T>
+__global__ __launch_bounds__(256) void k_comp_scores_listed(const T* __restrict__ Qi, const int* __restrict__ dq, int Qn,
+                                                            const T* __restrict__ Ci, const int* __restrict__ dc,
+                                                            int64_t N, int H, int W, const int64_t* __restrict__ ids,
+                                                            int C, const double* __restrict__ wt, int ML, int nw_cap,
+                                                            double* __restrict__ out, double* __restrict__ parts) {
+  extern __shared__ double sm[];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  double* wsc = sm + (size_t)wv * nw_cap;
+  double* qn = sm + (size_t)4 * nw_cap;
+  T* qf = reinterpret_cast<T*>(sm + (size_t)5 * nw_cap);
+  const int img = H * W;
+  const int j0 = (int)blockIdx.x * kCompCand;
+  const int j1 = j0 + kCompCand < C ? j0 + kCompCand : C;
+  for (int q = blockIdx.y; q < Qn; q += gridDim.y) {
+    int hq_, Lq;
+    unsigned maskq;
+    CompWin gq;
+    comp_stage_query(Qi, dq, q, H, W, qf, qn, hq_, Lq, maskq, gq);
+    for (int j = j0 + wv; j < j1; j += 4) {
+      const int64_t o = (int64_t)q * C + j;
+      const int64_t cand = ids[o];  // wave-uniform
+      double pt[3] = {0.0, 0.0, 0.0};
+      double score = -INFINITY;
+      if (cand >= 0 && cand < N) {
+        const int hc = min(max(dc[4 * cand], 1), H);
+        score = comp_pair(qf, hq_, Lq, maskq, gq, gq.count(), qn, wsc, Ci + cand * img, hc, dc[4 * cand + 1],
+                          (unsigned)dc[4 * cand + 3], H, W, wt, ML, lane, pt);
+      }
+      if (lane == 0) {
+        out[o] = score;
+        if (parts) {
+          parts[3 * o + 0] = pt[0];
+          parts[3 * o + 1] = pt[1];
+          parts[3 * o + 2] = pt[2];
+        }
+      }
+    }
+  }
+}
+
+// ---- list ranking and neighbour windows ---------------------------------------------------------------------
+constexpr int kListMax = 1024;  // entries of one list: one per thread of the workgroup
+
+// One workgroup per query: entry j's rank = the eligible entries that precede it in (score desc, position asc);
+// ranks below k are written at their rank, the rest of the row is padded.  Ineligible entries sit in LDS as NaN.
+__global__ __launch_bounds__(kListMax) void k_list_topk(const double* __restrict__ scores,
+                                                        const int64_t* __restrict__ ids, int C, int k, double thr,
+                                                        int mode, double* __restrict__ out_score,
+                                                        int64_t* __restrict__ out_id, int* __restrict__ out_count) {
+  __shared__ double s[kListMax];
+  __shared__ int total;
+  const int q = blockIdx.x, j = threadIdx.x;
+  if (j == 0) total = 0;
+  double v = nan("");
+  int64_t id = -1;
+  if (j < C) {
+    const double x = scores[(int64_t)q * C + j];
+    id = ids[(int64_t)q * C + j];
+    const bool ok = id >= 0 && x == x && (mode == 0 || (mode == 1 ? x >= thr : x > thr));
+    if (ok) v = x;
+    s[j] = v;
+  }
+  __syncthreads();
+  const bool mine = v == v;
+  if (mine) {
+    int rank = 0;
+    for (int i = 0; i < C; ++i) {
+      const double o = s[i];  // NaN compares false both ways
+      rank += (o > v || (o == v && i < j)) ? 1 : 0;
+    }
+    if (rank < k) {
+      out_score[(int64_t)q * k + rank] = v;
+      out_id[(int64_t)q * k + rank] = id;
+    }
+    atomicAdd(&total, 1);
+  }
+  __syncthreads();
+  const int n = total < k ? total : k;
+  for (int r = n + j; r < k; r += kListMax) {
+    out_score[(int64_t)q * k + r] = -INFINITY;
+    out_id[(int64_t)q * k + r] = -1;
+  }
+  if (j == 0) out_count[q] = n;
+}
+
+// One workgroup per query: thread j = window slot j % window of head j / window -> its frame (or -1) in LDS; a
+// slot is dropped when an earlier slot holds the same frame; the kept slots are compacted by a prefix count.
+__global__ __launch_bounds__(kListMax) void k_list_windows(const int64_t* __restrict__ heads, int C0, int64_t N,
+                                                           int window, int64_t* __restrict__ out,
+                                                           int* __restrict__ out_count) {
+  __shared__ int64_t f[kListMax];
+  __shared__ int keep[kListMax];
+  __shared__ int total;
+  const int q = blockIdx.x, j = threadIdx.x, n = C0 * window;
+  int64_t mine = -1;
+  if (j < n) {
+    const int64_t h = heads[(int64_t)q * C0 + j / window];
+    if (h >= 0) {
+      const int64_t half = window / 2;
+      const int64_t start = h - half > 0 ? h - half : 0;
+      const int64_t end = start + window < h + half + 1 ? start + window : h + half + 1;
+      const int64_t x = start + j % window;
+      if (x < end && x < N) mine = x;
+    }
+    f[j] = mine;
+  }
+  __syncthreads();
+  int kept = 0;
+  if (mine >= 0) {
+    kept = 1;
+    for (int i = 0; i < j; ++i)
+      if (f[i] == mine) { kept = 0; break; }
+  }
+  if (j < n) keep[j] = kept;
+  __syncthreads();
+  int pos = 0;
+  if (j < n) {
+    for (int i = 0; i < j; ++i) pos += keep[i];
+    if (kept) out[(int64_t)q * n + pos] = mine;
+  }
+  if (j == n - 1) total = pos + kept;
+  __syncthreads();
+  if (j >= total && j < n) out[(int64_t)q * n + j] = -1;
+  if (j == 0) out_count[q] = total;
 }
 
 // ---- composite rows -----------------------------------------------------------------------------------------
@@ -437,6 +603,59 @@ int hq_comp_scores(int dtype, const void* q, const int32_t* desc_q, int Q, const
     hipLaunchKernelGGL(k_comp_scores<double>, grid, dim3(256), lds, s, (const double*)q, desc_q, Q, (const double*)c,
                        desc_c, N, H, W, weights, max_levels, nw_cap, out, parts);
   }
+  HQ_CHECK_LAUNCH();
+  return HQ_OK;
+}
+
+int hq_comp_scores_listed(int dtype, const void* q, const int32_t* desc_q, int Q, const void* c, const int32_t* desc_c,
+                          int64_t N, int H, int W, const int64_t* ids, int C, const double* weights, int max_levels,
+                          double* out, double* parts, hq_stream_t stream) {
+  if (Q < 0 || N < 0 || C < 0 || H <= 0 || W <= 0 || max_levels < 0) return fail(HQ_E_INVALID, "bad shape");
+  if (dtype != HQ_F32 && dtype != HQ_F64) return fail(HQ_E_UNSUPPORTED, "dtype %d (float32 / float64)", dtype);
+  if (Q == 0 || C == 0) return HQ_OK;
+  // (N = 0: every entry is a pad, c and desc_c are never read)
+  if (!q || !desc_q || !ids || !out || (N > 0 && (!c || !desc_c)) || (max_levels > 0 && !weights))
+    return fail(HQ_E_INVALID, "null buffer");
+  if ((int64_t)H * W > (1 << 24)) return fail(HQ_E_UNSUPPORTED, "frame %dx%d too large", H, W);
+  const int nw_cap = comp_max_windows(H, W);
+  const size_t lds = (size_t)5 * nw_cap * 8 + (size_t)H * W * (dtype == HQ_F32 ? 4 : 8);
+  if (lds > kCompLds) return fail(HQ_E_UNSUPPORTED, "frame %dx%d: query and window lists exceed 160 KiB of LDS", H, W);
+  const dim3 grid((unsigned)((C + kCompCand - 1) / kCompCand), (unsigned)(Q < 65535 ? Q : 65535));
+  const hipStream_t s = (hipStream_t)stream;
+  if (dtype == HQ_F32) {
+    HQ_CHECK_HIP(hipFuncSetAttribute((const void*)k_comp_scores_listed<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_comp_scores_listed<float>, grid, dim3(256), lds, s, (const float*)q, desc_q, Q, (const float*)c,
+                       desc_c, N, H, W, ids, C, weights, max_levels, nw_cap, out, parts);
+  } else {
+    HQ_CHECK_HIP(hipFuncSetAttribute((const void*)k_comp_scores_listed<double>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_comp_scores_listed<double>, grid, dim3(256), lds, s, (const double*)q, desc_q, Q,
+                       (const double*)c, desc_c, N, H, W, ids, C, weights, max_levels, nw_cap, out, parts);
+  }
+  HQ_CHECK_LAUNCH();
+  return HQ_OK;
+}
+
+int hq_list_topk(const double* scores, const int64_t* ids, int Q, int C, int k, double threshold, int thr_mode,
+                 double* out_score, int64_t* out_id, int32_t* out_count, hq_stream_t stream) {
+  if (Q < 0 || thr_mode < 0 || thr_mode > 2) return fail(HQ_E_INVALID, "bad shape");
+  if (C < 1 || C > kListMax || k < 1) return fail(HQ_E_UNSUPPORTED, "list of %d entries, k = %d (1 .. %d, k >= 1)", C, k, kListMax);
+  if (Q == 0) return HQ_OK;
+  if (!scores || !ids || !out_score || !out_id || !out_count) return fail(HQ_E_INVALID, "null buffer");
+  hipLaunchKernelGGL(k_list_topk, dim3((unsigned)Q), dim3(kListMax), 0, (hipStream_t)stream, scores, ids, C, k, threshold,
+                     thr_mode, out_score, out_id, out_count);
+  HQ_CHECK_LAUNCH();
+  return HQ_OK;
+}
+
+int hq_list_windows(const int64_t* heads, int Q, int C0, int64_t N, int window, int64_t* out, int32_t* out_count,
+                    hq_stream_t stream) {
+  if (Q < 0 || C0 < 0 || N < 0) return fail(HQ_E_INVALID, "bad shape");
+  if (window < 1 || window > 64 || (int64_t)C0 * window > kListMax)
+    return fail(HQ_E_UNSUPPORTED, "window %d over %d heads (1 .. 64, at most %d entries)", window, C0, kListMax);
+  if (Q == 0 || C0 == 0) return HQ_OK;
+  if (!heads || !out || !out_count) return fail(HQ_E_INVALID, "null buffer");
+  hipLaunchKernelGGL(k_list_windows, dim3((unsigned)Q), dim3(kListMax), 0, (hipStream_t)stream, heads, C0, N, window, out,
+                     out_count);
   HQ_CHECK_LAUNCH();
   return HQ_OK;
 }

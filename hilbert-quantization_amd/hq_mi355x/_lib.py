@@ -138,6 +138,9 @@ SIGNATURES = {
     "hq_cosqf_topk": (_i, [_p, _p, _i, _p, _p, _i64, _i, _i, _d, _i, _i64, _p, _sz, _p, _p, _p]),
     "hq_comp_describe": (_i, [_i, _p, _i64, _i, _i, _p, _p]),
     "hq_comp_scores": (_i, [_i, _p, _p, _i, _p, _p, _i64, _i, _i, _p, _i, _p, _p, _p]),
+    "hq_comp_scores_listed": (_i, [_i, _p, _p, _i, _p, _p, _i64, _i, _i, _p, _i, _p, _i, _p, _p, _p]),
+    "hq_list_topk": (_i, [_p, _p, _i, _i, _i, _d, _i, _p, _p, _p, _p]),
+    "hq_list_windows": (_i, [_p, _i, _i, _i64, _i, _p, _p, _p]),
     "hq_comp_layout": (_i, [_i, _i, _i, _p]),
     "hq_comp_padded_k": (_i, [_i, _i, _i]),
     "hq_comp_prepare": (_i, [_p, _i64, _i64, _i, _i, _i, _i, _p, _p, _p, _p]),

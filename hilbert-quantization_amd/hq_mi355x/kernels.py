@@ -1147,6 +1147,71 @@ def comp_scores(q, desc_q, c, desc_c, weights, parts: bool = False, exc=None):
     return (out, pt) if parts else out
 
 
+LIST_MAX = 1024
+
+
+def comp_scores_listed(q, desc_q, c, desc_c, ids, weights, parts: bool = False, exc=None):
+    """comp_scores through an id list (hq_comp_scores_listed, one launch): ids int64 [Q, C] -> device f64 [Q, C],
+    entry (a, j) bit for bit what comp_scores writes for (query a, frame ids[a, j]); the frames are read in place.
+    An id < 0 or >= N is a pad: -inf (parts 0.0).  parts=True adds the components [Q, C, 3]."""
+    t = torch()
+    q3, c3 = _frames3(q), _frames3(c)
+    if q3.dtype != c3.dtype or q3.shape[1:] != c3.shape[1:]:
+        raise ValueError(f"frames differ: {tuple(q3.shape[1:])} {q3.dtype} vs {tuple(c3.shape[1:])} {c3.dtype}")
+    Q, H, W = (int(d) for d in q3.shape)
+    N = int(c3.shape[0])
+    il = _contig(ids.to(t.int64))
+    if il.dim() != 2 or int(il.shape[0]) != Q:
+        raise ValueError(f"ids {tuple(il.shape)} for {Q} queries")
+    C = int(il.shape[1])
+    wt = np.ascontiguousarray(weights, dtype=np.float64)
+    ML = int(wt.shape[1]) if wt.ndim == 2 and wt.shape[0] > 1 else 0
+    wd = t.as_tensor(wt.reshape(-1) if ML else np.zeros(1), device=q3.device)
+    out = t.empty((Q, C), dtype=t.float64, device=q3.device)
+    pt = t.empty((Q, C, 3), dtype=t.float64, device=q3.device) if parts else None
+    if Q and C:
+        _chk(_L().hq_comp_scores_listed(dtype_code(q3.dtype), ptr(q3), ptr(_contig(desc_q)), Q, ptr(c3) if N else None,
+                                        ptr(_contig(desc_c)) if N else None, N, H, W, ptr(il), C, ptr(wd), ML,
+                                        ptr(out), ptr(pt) if parts else None, stream()), exc)
+    return (out, pt) if parts else out
+
+
+def list_topk(scores, ids, k: int, threshold: float = 0.0, thr_mode: int = 0, exc=None):
+    """The first k entries of every list in (score desc, list position asc) order (hq_list_topk, one launch):
+    scores f64 [Q, C], ids int64 [Q, C] (id < 0: a pad; NaN scores never rank; thr_mode 0 none, 1 >=, 2 >)
+    -> device (scores [Q, k] f64, ids [Q, k] i64, counts [Q] i32), -inf / -1 padded.  C <= 1024."""
+    t = torch()
+    sc = _contig(scores.to(t.float64))
+    il = _contig(ids.to(t.int64))
+    if sc.dim() != 2 or sc.shape != il.shape:
+        raise ValueError(f"scores {tuple(sc.shape)} and ids {tuple(il.shape)}")
+    Q, C = (int(d) for d in sc.shape)
+    k = int(k)
+    os_ = t.empty((Q, max(k, 0)), dtype=t.float64, device=sc.device)
+    oi = t.empty((Q, max(k, 0)), dtype=t.int64, device=sc.device)
+    cnt = t.empty(Q, dtype=t.int32, device=sc.device)
+    _chk(_L().hq_list_topk(ptr(sc), ptr(il), Q, C, k, float(threshold), int(thr_mode), ptr(os_), ptr(oi), ptr(cnt),
+                           stream()), exc)
+    return os_, oi, cnt
+
+
+def list_windows(heads, N: int, window: int, exc=None):
+    """Every head frame widened to its window of consecutive frames (hq_list_windows, one launch;
+    FrameCacheManager.cache_consecutive_frames, rag/search/frame_cache.py:66-72): heads int64 [Q, C0] (-1: no head)
+    -> device (frames [Q, C0 window] i64: first appearances in head order, each window ascending, frames >= N
+    dropped, -1 padded; counts [Q] i32).  window <= 64, C0 window <= 1024."""
+    t = torch()
+    hd = _contig(heads.to(t.int64))
+    if hd.dim() != 2:
+        raise ValueError(f"heads {tuple(hd.shape)} must be [Q, C0]")
+    Q, C0 = (int(d) for d in hd.shape)
+    window = int(window)
+    out = t.empty((Q, C0 * max(window, 0)), dtype=t.int64, device=hd.device)
+    cnt = t.zeros(Q, dtype=t.int32, device=hd.device)
+    _chk(_L().hq_list_windows(ptr(hd), Q, C0, int(N), window, ptr(out), ptr(cnt), stream()), exc)
+    return out, cnt
+
+
 COMP_LAYOUT_FIELDS = ("K", "L", "ws", "stride", "ni", "nj", "off_win", "off_orig", "off_levels", "off_const",
                       "off_orig_ind", "off_win_ind")
 

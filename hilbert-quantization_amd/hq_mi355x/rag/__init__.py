@@ -11,6 +11,7 @@ from .hierarchical_index_generator import HierarchicalIndexGenerator
 from .similarity import (ComprehensiveFrameCorpus, FrameCosineCorpus, HierarchicalFrameCorpus, QuantizedFrameCorpus,
                          apply_progressive_threshold, progressive_hierarchical_search,
                          calculate_comprehensive_similarity, calculate_embedding_similarity, comprehensive_scores,
+                         comprehensive_scores_listed,
                          similarity_weights,
                          calculate_embedding_cosine_similarity, calculate_granularity_weights, calculate_spatial_locality_similarity,
                          compare_multi_level_indices, compare_single_level_indices, cosine_scores_batch,
@@ -18,7 +19,7 @@ from .similarity import (ComprehensiveFrameCorpus, FrameCosineCorpus, Hierarchic
                          progressive_threshold, progressive_threshold_batch, spatial_locality_scores)
 
 __all__ = ["ComprehensiveFrameCorpus", "HierarchicalFrameCorpus", "progressive_hierarchical_search", "calculate_comprehensive_similarity", "calculate_embedding_similarity",
-           "comprehensive_scores", "similarity_weights", "FrameCosineCorpus", "HilbertCurveMapperImpl", "HierarchicalIndexGenerator", "QuantizedFrameCorpus",
+           "comprehensive_scores", "comprehensive_scores_listed", "similarity_weights", "FrameCosineCorpus", "HilbertCurveMapperImpl", "HierarchicalIndexGenerator", "QuantizedFrameCorpus",
            "apply_progressive_threshold",
            "calculate_embedding_cosine_similarity", "calculate_granularity_weights",
            "calculate_spatial_locality_similarity", "compare_multi_level_indices", "compare_single_level_indices",

@@ -168,16 +168,18 @@ class DualStorageCorpus:
                 out[qi.view(-1, 1), ci.view(1, -1)] = s
         return out
 
-    def search(self, query_frames, k: int = 10, method: str = "spatial") -> List[List[Tuple[VideoFrameMetadata, float]]]:
+    def search(self, query_frames, k: int = 10, method: str = "spatial",
+               window: int = 0) -> List[List[Tuple[VideoFrameMetadata, float]]]:
         """Top-k stored frames per query by (score desc, frame order asc).  method="progressive": the engine's
         workflow instead (HierarchicalFrameCorpus.search: the progressive hierarchical cascade, then the
-        comprehensive score of its first 2 k candidates, score >= 0.1, ties in the cascade's order); the store's
-        packed index rows are prepared on the first such call and stay resident."""
+        comprehensive score of its first 2 k candidates, score >= 0.1, ties in the cascade's order; window = w >= 1
+        widens every candidate to w consecutive frames first, the engine's step 3); the store's packed index rows
+        are prepared on the first such call and stay resident."""
         if method == "progressive":
             if self._hier is None:
                 self._hier = S.HierarchicalFrameCorpus(self.frames)
             q = to_dev(query_frames)
-            s, ids = self._hier.search(q.to(self.frames.dtype), int(k))
+            s, ids = self._hier.search(q.to(self.frames.dtype), int(k), window=int(window))
             s, ids = to_np(s), to_np(ids)
             return [[(self.metadata[int(i)], float(v)) for v, i in zip(s[r], ids[r]) if i >= 0] for r in range(len(s))]
         sc = self.scores(query_frames, method)

@@ -573,6 +573,58 @@ def _comp_exact(q3, dq_dev, dq, c3, dc_dev, dc, parts: bool = False):
     return K.comp_scores(q3, dq_dev, c3, dc_dev, _weight_table(ml), parts)
 
 
+def _index_widths(desc: np.ndarray) -> frozenset:
+    """The index widths of the frames that have index rows (host descriptors [N, 4])."""
+    return frozenset(desc[desc[:, 1] >= 1, 2].tolist())
+
+
+def _windows_host(head: np.ndarray, N: int, window: int) -> np.ndarray:
+    """hq_list_windows' rule for one host list (the per-query route of lists beyond the kernel's 1024 entries)."""
+    half, seen, out = window // 2, set(), []
+    for f in head.tolist():
+        start = max(0, f - half)
+        for x in range(start, min(start + window, f + half + 1, N)):
+            if x not in seen:
+                seen.add(x)
+                out.append(x)
+    return np.array(out, dtype=np.int64)
+
+
+def _comp_listed(q3, dq_dev, dq, c3, dc_dev, ml_c: int, widths_c: frozenset, ids, parts: bool = False):
+    """The exact scores of the listed frames (hq_comp_scores_listed, the frames read in place), the weight table
+    sized by the larger of the store's and the batch's level count (row M does not depend on the number of
+    columns).  The width error of _check_widths, for the listed pairs only: when the queries and the whole store
+    share one index width nothing can differ and nothing is read back; otherwise the listed frames' descriptors
+    are gathered on the device and one flag is read."""
+    wq = _index_widths(dq)
+    if wq and widths_c and len(wq | widths_c) > 1:
+        N = int(c3.shape[0])
+        d = dc_dev[ids.clamp(0, N - 1)]
+        qd = dq_dev.unsqueeze(1)
+        differ = ((ids >= 0) & (ids < N) & (d[..., 1] >= 1) & (qd[..., 1] >= 1) & (d[..., 2] != qd[..., 2])).any()
+        if bool(to_np(differ)):
+            raise ValueError(_WIDTH_ERROR)
+    ml = max(int(ml_c), int(dq[:, 1].max(initial=0)))
+    return K.comp_scores_listed(q3, dq_dev, c3, dc_dev, ids, _weight_table(ml), parts)
+
+
+def comprehensive_scores_listed(queries, frames, ids, parts: bool = False):
+    """comprehensive_scores through an id list: ids int64 [Q, C] -> device f64 [Q, C], entry (a, j) bit for bit the
+    dense score of (query a, frame ids[a, j]); an id < 0 or >= N is a pad (-inf, parts 0.0).  The stored frames are
+    read in place, one scoring launch.  ValueError with the reference's message when a listed pair whose frames
+    both have index rows differs in index width."""
+    t = torch()
+    q3, c3 = _comp_frames(queries), _comp_frames(frames)
+    if q3.dtype != c3.dtype:
+        q3, c3 = q3.to(t.float64), c3.to(t.float64)
+    if q3.shape[1:] != c3.shape[1:]:
+        raise ValueError(f"frame shapes differ: {tuple(q3.shape[1:])} vs {tuple(c3.shape[1:])}")
+    dq_dev, dc_dev = K.comp_describe(q3), K.comp_describe(c3)
+    dc = to_np(dc_dev)
+    return _comp_listed(q3, dq_dev, to_np(dq_dev), c3, dc_dev, dc[:, 1].max(initial=0), _index_widths(dc),
+                        to_dev(ids, t.int64), parts)
+
+
 def comprehensive_scores(queries, frames, parts: bool = False):
     """_calculate_comprehensive_similarity (engine.py:516-575) of every query frame [Q, H, W] against every stored
     enhanced frame [N, H, W] -> device f64 [Q, N]; parts=True adds the components [Q, N, 3] (hierarchical,
@@ -745,6 +797,23 @@ class ComprehensiveFrameCorpus:
             lambda Q, dev: (t.full((Q, k), float("-inf"), dtype=t.float64, device=dev),
                             t.full((Q, k), -1, dtype=t.int64, device=dev)))
 
+    def rescore(self, queries, ids):
+        """The exact scores of the listed frames: ids int64 [Q, C] (the list of a fused search, say) -> device f64
+        [Q, C], bit for bit comprehensive_scores' values for those pairs, -inf where the id is < 0 or >= N
+        (hq_comp_scores_listed: one launch, the frames read in place).  Needs the raw frames: a store that is not
+        fused, or keep_frames=True."""
+        t = torch()
+        if self._frames is None:
+            raise ValueError("rescore needs the raw frames and the corpus was built without keep_frames=True")
+        q3 = _comp_frames(queries)
+        if tuple(q3.shape[1:]) != (self.H, self.W):
+            raise ValueError(f"query frames {tuple(q3.shape[1:])} are not [{self.H}, {self.W}]")
+        if q3.dtype != self.dtype:
+            q3 = q3.to(self.dtype)
+        dq_dev = K.comp_describe(q3)
+        return _comp_listed(q3, dq_dev, to_np(dq_dev), self._frames, self._desc_dev, self._desc[:, 1].max(initial=0),
+                            _index_widths(self._desc), to_dev(ids, t.int64))
+
 
 # ------------------------------------------------------------------ progressive hierarchical search (:51-95)
 
@@ -755,7 +824,8 @@ class HierarchicalFrameCorpus:
     comprehensive score.  The store is described (hq_comp_describe) and its index rows are packed (hq_hier_prepare:
     compacted, trimmed, float64) and kept resident, max_levels x W x 8 bytes per frame plus the lengths
     (`resident_bytes`); keep_frames=True (the default) keeps the raw frames too, which search() needs for the
-    comprehensive re-rank.
+    comprehensive re-rank: search() is the engine's whole workflow (cascade, neighbour windows, exact scores of the
+    list, threshold and cut) for a query batch, on the device.
 
     The cascade: level l orders the survivors by (s_l desc, s_{l-1} desc, ..., s_0 desc, id asc) and
     keeps the first max(1, int(n_prev ratio_l)) of those with s_l >= thr_l (progressive_threshold's tables).  It runs
@@ -776,6 +846,9 @@ class HierarchicalFrameCorpus:
         self._frames = x if keep_frames else None
         self._desc_dev = desc_dev if keep_frames else None
         self._desc = to_np(desc_dev) if keep_frames else None
+        if keep_frames:  # what the listed re-rank needs of the whole store: its level count and index widths
+            self._ml = int(self._desc[:, 1].max(initial=0))
+            self._widths = _index_widths(self._desc)
 
     def __len__(self) -> int:
         return self.N
@@ -826,14 +899,8 @@ class HierarchicalFrameCorpus:
             raise ValueError("candidates() takes one query frame [H, W]")
         return [int(i) for i in self._candidates(qr, 0)]
 
-    def search(self, queries, k: int = 10, threshold: float = 0.1):
-        """The engine's search workflow (search_similar_documents_with_caching, engine.py:754-781, steps 2, 4, 5) for
-        queries [Q, H, W] (or one frame): the first 2 k candidates of the cascade, their comprehensive scores by the
-        exact route (hq_comp_scores on the gathered frames), a stable order by score descending (ties keep the
-        cascade's order), score >= threshold, the first k -> device (scores [Q, k] f64, ids [Q, k] i64), -inf / -1
-        padded.  One scoring launch per query.  ValueError with the reference's message when a query and a candidate
-        with index rows differ in index width."""
-        t = torch()
+    def _search_inputs(self, queries, k):
+        """(k, query frames in the store's dtype, their descriptors on the device and the host, their packed rows)."""
         k = int(k)
         if k < 1:
             raise ValueError(f"k = {k}")
@@ -841,11 +908,18 @@ class HierarchicalFrameCorpus:
             raise ValueError("HierarchicalFrameCorpus.search needs the raw frames for the comprehensive re-rank: "
                              "build the corpus with keep_frames=True")
         q3, dq_dev, qr = self._queries(queries)
-        Q = qr.N
         if q3.dtype != self.dtype:
             q3 = q3.to(self.dtype)
             dq_dev = K.comp_describe(q3)
-        dq = to_np(dq_dev)
+        return k, q3, dq_dev, to_np(dq_dev), qr
+
+    def _search_per_query(self, queries, k: int = 10, threshold: float = 0.1, window: int = 0):
+        """search() with a host loop over the queries: the list heads copied to the host, then per query the raw
+        frames of its list gathered, one hq_comp_scores launch and a NumPy stable sort.  The route of lists beyond
+        hq_list_topk's 1024 entries, and the yardstick search() is tested against."""
+        t = torch()
+        k, q3, dq_dev, dq, qr = self._search_inputs(queries, k)
+        Q = qr.N
         out_s = np.full((Q, k), -np.inf)
         out_i = np.full((Q, k), -1, dtype=np.int64)
         if 2 * k <= K.HIER_MAX_K:
@@ -853,6 +927,8 @@ class HierarchicalFrameCorpus:
             heads = [r[r >= 0] for r in to_np(ids)]
         else:
             heads = [self._candidates(qr, a)[:2 * k] for a in range(Q)]
+        if window:
+            heads = [_windows_host(h, self.N, int(window)) for h in heads]
         for a, head in enumerate(heads):
             if not len(head):
                 continue
@@ -863,6 +939,37 @@ class HierarchicalFrameCorpus:
             order = order[sc[order] >= threshold][:k]
             out_s[a, :len(order)], out_i[a, :len(order)] = sc[order], head[order]
         return to_dev(out_s), to_dev(out_i)
+
+    def search(self, queries, k: int = 10, threshold: float = 0.1, window: int = 0):
+        """The engine's search workflow (search_similar_documents_with_caching, engine.py:754-781, steps 2 - 5) for
+        queries [Q, H, W] (or one frame): the first 2 k candidates of the cascade (hq_hier_filter); window = w >= 1
+        (step 3, 10 in the engine): every candidate widened to its window of w consecutive frames, first appearances
+        kept in order (hq_list_windows), window = 0: the candidates themselves; the comprehensive scores of that
+        list by the exact route, the resident frames read through the list (hq_comp_scores_listed); a stable order
+        by score descending (ties keep the list's order), score >= threshold, the first k (hq_list_topk) -> device
+        (scores [Q, k] f64, ids [Q, k] i64), -inf / -1 padded.  The batch stays on the device: the number of
+        launches and of copies to the host does not grow with Q.  A list of more than 1024 entries (2 k w) takes a
+        host loop over the queries instead.  ValueError with the reference's message when a query and a listed
+        frame with index rows differ in index width."""
+        window = int(window)
+        if not 0 <= window <= 64:
+            raise ValueError(f"window = {window} (0 .. 64)")
+        if 2 * int(k) * max(window, 1) > K.LIST_MAX:
+            return self._search_per_query(queries, k, threshold, window)
+        k, q3, dq_dev, dq, qr = self._search_inputs(queries, k)
+        if 2 * k <= K.HIER_MAX_K:
+            _, lst, _, _ = K.hier_filter(qr, self._rows, self._thr, self._ratio, 2 * k)
+        else:  # the cascade kernel lists at most 64: longer heads are built per query on the host, then batched
+            head = np.full((qr.N, 2 * k), -1, dtype=np.int64)
+            for a in range(qr.N):
+                h = self._candidates(qr, a)[:2 * k]
+                head[a, :len(h)] = h
+            lst = to_dev(head)
+        if window:
+            lst, _ = K.list_windows(lst, self.N, window)
+        sc = _comp_listed(q3, dq_dev, dq, self._frames, self._desc_dev, self._ml, self._widths, lst)
+        s, ids, _ = K.list_topk(sc, lst, k, float(threshold), 1)
+        return s, ids
 
 
 def progressive_hierarchical_search(query_embedding, candidate_embeddings) -> List[int]:

@@ -791,11 +791,39 @@ int hq_threshold_select(const double* scores, const int64_t* ids, int Q, int64_t
  *   coefficient per section in LDS: 16 (H - h + 1 + n_windows) values must fit 160 KiB, i.e. at most
  *   1279 - (H - h) windows (67 x 64 frames: 961).  A profile beyond that, such as the RAG generator's 131 x 128
  *   frames (3969 windows, K = 84,243), is HQ_E_UNSUPPORTED: it cannot be fused, and since hq_comp_scores cannot
- *   stage such a frame either, callers refuse it (ComprehensiveFrameCorpus passes the message on).           */
+ *   stage such a frame either, callers refuse it (ComprehensiveFrameCorpus passes the message on).
+ * hq_comp_scores_listed: the same score through an id list.  ids int64 [Q, C], out f64 [Q, C], parts [Q, C, 3] or
+ *   NULL: out[a, j] is the value hq_comp_scores writes for the pair (query a, frame ids[a, j]), bit for bit,
+ *   whatever N, C or the entry's position (both kernels call one per-pair device function).  An entry with
+ *   ids[a, j] < 0 or >= N is a pad: out = -inf, its parts are 0.0, and no frame is read for it.  Repeated ids are
+ *   allowed and are scored independently.  No frames are copied: the kernel reads c + id H W.  LDS rule, refusal
+ *   message and argument checks are hq_comp_scores' (c and desc_c may be NULL when N = 0: every entry is a pad);
+ *   Q = 0 or C = 0 returns HQ_OK before any pointer is looked at.  One launch, no host synchronisation.
+ * hq_list_topk: scores f64 [Q, C] and ids int64 [Q, C] -> the first k entries of every row in (score descending,
+ *   list position ascending) order: out_score / out_id [Q, k], padded with -inf / -1, out_count int32 [Q] = the
+ *   number written.  An entry is eligible when its id is >= 0, its score is not NaN, and it passes thr_mode (0
+ *   none, 1 >=, 2 >, as hq_select_topk).  -0.0 and 0.0 compare equal, so position decides between them.  This is
+ *   the reference's stable sort by score over a list whose order carries meaning (the cascade's), then the
+ *   threshold and the cut; hq_select_topk breaks ties by id and does not specify NaN.  1 <= C <= 1024 and 1 <= k,
+ *   anything beyond is HQ_E_UNSUPPORTED.  One workgroup per query, O(C^2) rank counting in LDS, one launch.
+ * hq_list_windows: heads int64 [Q, C0] (-1 allowed anywhere) -> out int64 [Q, C0 window]: each head f >= 0 widened
+ *   to its window of consecutive frames (FrameCacheManager.cache_consecutive_frames, rag/search/frame_cache.py:
+ *   66-72): half = window / 2, start = max(0, f - half), end = min(start + window, f + half + 1), frames start ..
+ *   end - 1, those >= N dropped.  The row is the windows' frames in head order, each window ascending, keeping only
+ *   a frame's first appearance, compacted to the front and -1 padded; out_count int32 [Q] = its length.  window = 1
+ *   returns the heads, deduplicated.  1 <= window <= 64 and C0 window <= 1024, anything else is HQ_E_UNSUPPORTED.
+ *   One workgroup per query, one launch.                                                                       */
 int hq_comp_describe(int dtype, const void* imgs, int64_t N, int H, int W, int32_t* desc, hq_stream_t stream);
 int hq_comp_scores(int dtype, const void* q, const int32_t* desc_q, int Q, const void* c, const int32_t* desc_c,
                    int64_t N, int H, int W, const double* weights, int max_levels, double* out, double* parts,
                    hq_stream_t stream);
+int hq_comp_scores_listed(int dtype, const void* q, const int32_t* desc_q, int Q, const void* c, const int32_t* desc_c,
+                          int64_t N, int H, int W, const int64_t* ids, int C, const double* weights, int max_levels,
+                          double* out, double* parts, hq_stream_t stream);
+int hq_list_topk(const double* scores, const int64_t* ids, int Q, int C, int k, double threshold, int thr_mode,
+                 double* out_score, int64_t* out_id, int32_t* out_count, hq_stream_t stream);
+int hq_list_windows(const int64_t* heads, int Q, int C0, int64_t N, int window, int64_t* out, int32_t* out_count,
+                    hq_stream_t stream);
 int hq_comp_layout(int H, int W, int h, int32_t* out);
 int hq_comp_padded_k(int H, int W, int h);
 int hq_comp_prepare(const float* imgs, int64_t N, int64_t ld, int H, int W, int h, int side, const double* level_coef,
