@@ -147,6 +147,15 @@ SIGNATURES = {
     "hq_hier_prepare": (_i, [_i, _p, _i64, _i64, _i, _i, _p, _i, _p, _p, _p]),
     "hq_hier_workspace_size": (_sz, [_i, _i64, _i]),
     "hq_hier_filter": (_i, [_p, _p, _p, _i, _p, _p, _i64, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p, _p]),
+    "hq_order_padded_rows": (_i64, [_i64]),
+    "hq_order_padded_len": (_i, [_i]),
+    "hq_order_prepare": (_i, [_p, _i64, _i64, _i, _p, _p, _p]),
+    "hq_order_sims": (_i, [_p, _p, _p, _i64, _i64, _p, _p, _p, _i64, _i64, _i, _p, _i64, _p]),
+    "hq_order_start": (_i, [_p, _i64, _i64, _i, _p, _p]),
+    "hq_order_greedy_workspace_size": (_sz, [_i64]),
+    "hq_order_greedy": (_i, [_p, _p, _p, _i64, _i64, _i, _p, _sz, _p, _p, _p]),
+    "hq_order_pairs": (_i, [_p, _p, _p, _i64, _i64, _i, _p, _p, _p, _p]),
+    "hq_order_insert": (_i, [_p, _i64, _i, _i64, _p, _p, _p]),
 }
 
 _lock = threading.Lock()

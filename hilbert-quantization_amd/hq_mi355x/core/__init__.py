@@ -8,8 +8,11 @@ from .search_engine import ProgressiveSimilaritySearchEngine, LevelConfig, Index
 from .pipeline import QuantizationPipeline, quantize_batch
 from .precomputed_hilbert_index import (PrecomputedHilbertIndexer, PrecomputedSimilaritySearchEngine,
                                         PrecomputedIndex, PrecomputedLevel)
+from .frame_order import (FrameOrdering, sort_frames_by_hierarchical_indices, frame_ordering_metrics,
+                          find_optimal_insertion_position)
 
 __all__ = ["PowerOf4DimensionCalculator", "HilbertCurveMapper", "StreamingHilbertIndexGenerator",
            "HierarchicalIndexGeneratorImpl", "MPEGAICompressorImpl", "ProgressiveSimilaritySearchEngine",
            "LevelConfig", "IndexCorpus", "QuantizationPipeline", "quantize_batch", "PrecomputedHilbertIndexer",
-           "PrecomputedSimilaritySearchEngine", "PrecomputedIndex", "PrecomputedLevel"]
+           "PrecomputedSimilaritySearchEngine", "PrecomputedIndex", "PrecomputedLevel", "FrameOrdering",
+           "sort_frames_by_hierarchical_indices", "frame_ordering_metrics", "find_optimal_insertion_position"]

@@ -98,3 +98,27 @@ class FrameStoreCorpus:
         base = self.corpus.id_base
         return [[(self.frames[int(i) - base][1], float(s)) for i, s in zip(ids[r], sc[r]) if i >= 0]
                 for r in range(len(q))]
+
+    def _video_frames(self, video_path: str) -> List[VideoFrameMetadata]:
+        fl = [fm for vp, fm in self.frames if vp == video_path]
+        if not fl:
+            raise ValueError(f"Video {video_path} not found in index")
+        return fl
+
+    def optimize_frame_ordering(self, video_path: Optional[str] = None):
+        """`optimize_frame_ordering` (core/video_storage.py:1150-1201) without the codec: per video the greedy
+        order (positions in the stored order), the ordering metrics before and after, and their difference in
+        temporal coherence.  One video -> its result dict; None -> {video_path: result} for every video."""
+        from .frame_order import FrameOrdering, _index_rows
+        if video_path is None:
+            return {vp: self.optimize_frame_ordering(vp) for vp in dict.fromkeys(vp for vp, _ in self.frames)}
+        fo = FrameOrdering(_index_rows(self._video_frames(video_path)))
+        order = to_np(fo.greedy_order()[0])
+        original, optimized = fo.metrics(), fo.metrics(order)
+        return {"order": order, "original_metrics": original, "optimized_metrics": optimized,
+                "temporal_coherence_improvement": optimized["temporal_coherence"] - original["temporal_coherence"]}
+
+    def insertion_position(self, query_indices, video_path: str) -> int:
+        """`_find_optimal_insertion_position` (:1751-1803) of a new frame's index vector in one video."""
+        from .frame_order import find_optimal_insertion_position
+        return find_optimal_insertion_position(query_indices, self._video_frames(video_path))

@@ -1594,3 +1594,88 @@ def cosqf_topk(q: CosQFRows, c: CosQRows, k: int, threshold: float = 0.0, thr_mo
     return _frame_topk(q, c, k, threshold, thr_mode, id_base, workspace_limit, exc, dense=cosqf_scores,
                        size=_L().hq_cosqf_topk_workspace_size, fused=_L().hq_cosqf_topk,
                        operands=lambda r: (r.Q8 if isinstance(r, CosQFRows) else r.X8, r.stats))
+
+
+# ------------------------------------------------------------------- greedy frame ordering (hq_order.hip)
+
+
+class OrderRows:
+    """Prepared index rows of the frame ordering (hq_order_prepare): X [N, L] f64 raw rows, Z [Np, Lp] centred
+    unit rows, flags [Np] u8 (bit 0 constant row, bit 1 pad, bit 2 a row holding a NaN or inf)."""
+
+    __slots__ = ("X", "Z", "flags", "N", "L")
+
+    def __init__(self, X, Z, flags, N, L):
+        self.X, self.Z, self.flags, self.N, self.L = X, Z, flags, int(N), int(L)
+
+
+def order_prepare(x, exc=None) -> OrderRows:
+    """Index rows [N, L] (or [L]) -> OrderRows.  Rows are widened to float64 (the reference's index vectors)."""
+    t = torch()
+    x2 = x.view(1, -1) if x.dim() == 1 else x
+    if x2.dtype != t.float64:
+        x2 = x2.to(t.float64)
+    x2 = _contig(x2)
+    N, L = int(x2.shape[0]), int(x2.shape[1])
+    Np, Lp = int(_L().hq_order_padded_rows(N)), int(_L().hq_order_padded_len(L))
+    Z = t.empty((max(Np, 1), max(Lp, 1)), dtype=t.float64, device=x2.device)
+    flags = t.empty(max(Np, 1), dtype=t.uint8, device=x2.device)
+    _chk(_L().hq_order_prepare(ptr(x2), N, L, L, ptr(Z), ptr(flags), stream()), exc)
+    return OrderRows(x2, Z, flags, N, L)
+
+
+def _order_same_len(a: OrderRows, b: OrderRows):
+    if a.L != b.L:
+        raise ValueError(f"index rows of different lengths {a.L} and {b.L}")
+
+
+def order_sims(q: OrderRows, c: OrderRows, exc=None):
+    """Pair similarity (core/video_storage.py:762-781) of every query row against every candidate row ->
+    f64 [Q, N] (hq_order_sims: one f64 MFMA contraction)."""
+    t = torch()
+    _order_same_len(q, c)
+    out = t.empty((q.N, c.N), dtype=t.float64, device=c.Z.device)
+    _chk(_L().hq_order_sims(ptr(q.Z), ptr(q.flags), ptr(q.X), q.L, q.N, ptr(c.Z), ptr(c.flags), ptr(c.X), c.L, c.N,
+                            c.L, ptr(out), c.N, stream()), exc)
+    return out
+
+
+def order_greedy(c: OrderRows, exc=None):
+    """Greedy nearest-neighbour chain from the row nearest the centroid (:1203-1277) -> (order [N] i64,
+    step_sims [N - 1] f64).  The N x N similarity matrix lives in the per-thread workspace."""
+    t = torch()
+    dev = c.Z.device
+    order = t.empty(c.N, dtype=t.int64, device=dev)
+    steps = t.empty(max(c.N - 1, 0), dtype=t.float64, device=dev)
+    wb = int(_L().hq_order_greedy_workspace_size(c.N))
+    ws = _workspace(wb, dev) if wb else None
+    _chk(_L().hq_order_greedy(ptr(c.Z), ptr(c.flags), ptr(c.X), c.L, c.N, c.L, ptr(ws), wb, ptr(order),
+                              ptr(steps) if c.N > 1 else None, stream()), exc)
+    return order, steps
+
+
+def order_pairs(c: OrderRows, order=None, exc=None):
+    """Neighbour-pair similarities of the rows taken in `order` (i64 [N] permutation on the device; None = stored
+    order) -> (pair_sims [N - 1] f64, stats [4] f64: average, variance, temporal coherence, ordering efficiency)."""
+    t = torch()
+    dev = c.Z.device
+    if order is not None and (order.dtype != t.int64 or int(order.numel()) != c.N):
+        raise ValueError(f"order must hold {c.N} int64 row ids")
+    pairs = t.empty(max(c.N - 1, 0), dtype=t.float64, device=dev)
+    stats = t.empty(4, dtype=t.float64, device=dev)
+    _chk(_L().hq_order_pairs(ptr(c.Z), ptr(c.flags), ptr(c.X), c.L, c.N, c.L,
+                             ptr(_contig(order)) if order is not None else None, ptr(pairs) if c.N > 1 else None,
+                             ptr(stats), stream()), exc)
+    return pairs, stats
+
+
+def order_insert(S, exc=None):
+    """Insertion positions (:1772-1803) for every row of a similarity matrix S [Q, N] -> (pos [Q] i64,
+    score [Q] f64)."""
+    t = torch()
+    S2 = _contig(S)
+    Q, N = int(S2.shape[0]), int(S2.shape[1])
+    pos = t.zeros(Q, dtype=t.int64, device=S2.device)
+    score = t.full((Q,), -1.0, dtype=t.float64, device=S2.device)
+    _chk(_L().hq_order_insert(ptr(S2), N, Q, N, ptr(pos), ptr(score), stream()), exc)
+    return pos, score

@@ -860,6 +860,54 @@ int hq_hier_filter(const double* q_rows, const int32_t* q_lens, const int32_t* L
                    int kout, void* ws, int64_t* out_count, int64_t* out_top_ids, double* out_top_scores,
                    uint8_t* out_alive, hq_stream_t stream);
 
+/* ---- greedy frame ordering of a video store (csrc/hq_order.hip) -----------------------------------
+ * replaces core/video_storage.py:1203-1277 (_sort_frames_by_hierarchical_indices), :1445-1522
+ * (get_frame_ordering_metrics, _calculate_ordering_efficiency) and :1751-1803
+ * (_find_optimal_insertion_position), all built on :762-781 (_calculate_hierarchical_similarity).
+ * Pair similarity of a query row a and a candidate row b (both L float64 values): when np.std(a) == 0 or
+ *   np.std(b) == 0 (decided in NumPy's summation order), 1.0 if np.allclose(a, b) — |a - b| <= 1e-8 + 1e-5 |b|
+ *   for every element, asymmetric in b — else 0.0; otherwise min(1, max(0, (r + 1) / 2)) with r the Pearson
+ *   correlation clipped to [-1, 1], computed as the dot product of the centred unit rows (x - mean) / |x - mean|:
+ *   within L 2^-53 of the exact value.  Contract: finite rows, 1 <= L <= 256 (else HQ_E_UNSUPPORTED), one length
+ *   per call; a row whose np.std is non-zero but below 1e-12 |mean| is outside the contract (the reference's
+ *   own value there is rounding noise).
+ * hq_order_padded_rows / hq_order_padded_len: N rounded up to a multiple of 16, L to a multiple of 4.
+ * hq_order_prepare: rows X [N, L] (row stride ldx) -> Z [padded rows, padded len] centred unit rows (a constant
+ *   row, a row holding a NaN or inf and every pad are zeros) and flags [padded rows]: bit 0 constant row, bit 1
+ *   pad row, bit 2 a row holding a NaN or inf (callers refuse such rows).
+ * hq_order_sims: S [M, N] (row stride ldS) = the similarity of query row i and candidate row j, the final value:
+ *   one f64 MFMA contraction Za Zb^T (v_mfma_f64_16x16x4f64, 64 x 64 tile per workgroup), entries with a constant
+ *   row or column evaluated by np.allclose on the raw rows Xa, Xb.  Bit-identical candidate rows get
+ *   bit-identical similarities.  At most 65535 * 64 query rows per call.
+ * hq_order_start (:1220-1247): start [1] = the row with the smallest |x - centroid| (column means over N),
+ *   strict <, lowest index on a tie; N = 1 gives 0.
+ * hq_order_greedy (:1249-1277): sims + start + the chain walk on one stream.  order [N] int64: order[0] the start
+ *   row, then repeatedly the unvisited row with the largest similarity to the last one (strict > from -1.0 in
+ *   row order: the lowest index wins a tie); step_sims [N - 1]: that similarity per step.  The walk is one
+ *   workgroup reading one row of the resident matrix per step.  workspace: hq_order_greedy_workspace_size(N)
+ *   bytes (8 padded_rows^2 + 16, 16-byte aligned; 0 for N outside 1 .. 16384); N > 16384 is HQ_E_UNSUPPORTED
+ *   (the reference's videos roll over at 10,000 frames, :83).
+ * hq_order_pairs (:1470-1490, :1492-1522): pair_sims [N - 1] = similarity of (order[q], order[q + 1]), or of
+ *   (q, q + 1) when order is NULL (an id outside [0, N) gives NaN); stats [4] = average neighbour similarity,
+ *   population variance, temporal coherence avg (1 - min(var, 1)), ordering efficiency max(0, 1 - mean(1 - s));
+ *   N = 1 writes 1, 0, 1, 1.
+ * hq_order_insert (:1772-1803): per query row of S [Q, N] the insertion position pos [Q] and its score [Q]:
+ *   position 0 scores s[0], i = 1 .. N-1 scores (s[i-1] + s[i]) / 2, N scores s[N-1]; the first maximum wins.
+ * Q = 0, M = 0 or N = 0 return HQ_OK without a launch (the outputs are not written).                        */
+int64_t hq_order_padded_rows(int64_t N);
+int hq_order_padded_len(int L);
+int hq_order_prepare(const double* X, int64_t N, int64_t ldx, int L, double* Z, uint8_t* flags, hq_stream_t stream);
+int hq_order_sims(const double* Za, const uint8_t* fa, const double* Xa, int64_t lda, int64_t M, const double* Zb,
+                  const uint8_t* fb, const double* Xb, int64_t ldb, int64_t N, int L, double* S, int64_t ldS,
+                  hq_stream_t stream);
+int hq_order_start(const double* X, int64_t ldx, int64_t N, int L, int64_t* start, hq_stream_t stream);
+size_t hq_order_greedy_workspace_size(int64_t N);
+int hq_order_greedy(const double* Z, const uint8_t* flags, const double* X, int64_t ldx, int64_t N, int L,
+                    void* workspace, size_t workspace_bytes, int64_t* order, double* step_sims, hq_stream_t stream);
+int hq_order_pairs(const double* Z, const uint8_t* flags, const double* X, int64_t ldx, int64_t N, int L,
+                   const int64_t* order, double* pair_sims, double* stats, hq_stream_t stream);
+int hq_order_insert(const double* S, int64_t ldS, int Q, int64_t N, int64_t* pos, double* score, hq_stream_t stream);
+
 /* ---- §8e: the sharded search's one collective (RCCL over xGMI) ----------------------------------
  * The corpus is split into contiguous global-id ranges, one per GPU (one process per GPU); each rank
  * answers the whole query batch against its shard and packs fixed-size top-k records, and ONE
