@@ -136,9 +136,11 @@ class HilbertQuantizer:
             raise QuantizationError(f"Unexpected error during quantization: {e}") from e
 
     def quantize_many(self, parameter_sets, model_ids: Optional[List[str]] = None,
-                      descriptions: Optional[List[str]] = None, validate: bool = True) -> List[QuantizedModel]:
-        """quantize() for many vectors in one batched device pass (same models, registry, indices)."""
-        return _ingest(self, parameter_sets, model_ids, descriptions, True, validate)
+                      descriptions: Optional[List[str]] = None, validate: bool = True,
+                      codec: str = "host") -> List[QuantizedModel]:
+        """quantize() for many vectors in one batched device pass (same models, registry, indices).
+        codec="device" encodes the JPEG payloads on the GPU as well (see _ingest)."""
+        return _ingest(self, parameter_sets, model_ids, descriptions, True, validate, codec=codec)
 
     def reconstruct(self, quantized_model: QuantizedModel, validate: bool = True) -> np.ndarray:
         try:
@@ -216,7 +218,7 @@ class HilbertQuantizer:
 
 
 def _ingest(hq: "HilbertQuantizer", parameter_sets, model_ids=None, descriptions=None, parallel: bool = True,
-            validate: bool = True, verbose: bool = False) -> List[QuantizedModel]:
+            validate: bool = True, verbose: bool = False, codec: str = "host") -> List[QuantizedModel]:
     """Batched HilbertQuantizer.quantize: the same QuantizedModels, registry entries,
     pre-computed indices and compressor state as calling quantize() model by model, in order.
 
@@ -225,14 +227,21 @@ def _ingest(hq: "HilbertQuantizer", parameter_sets, model_ids=None, descriptions
     JPEG stage (same call as core/compressor.py:71-80, byte-identical output) runs on a thread pool.
     Validation and efficiency failures surface at the same model, with the same exception, as the
     sequential path (models before it are quantized and registered first).  Other dtypes take the
-    per-model path.  `verbose` = the reference's per-model pre-computed-index prints."""
+    per-model path.  `verbose` = the reference's per-model pre-computed-index prints.
+
+    codec="device": the frames of every group are encoded where quantize_batch left them
+    (core.compressor.encode_jpeg_batch, hq_jpeg_encode) and are not copied to the host.  The payloads are
+    baseline JPEGs with the same quantisation table but the standard Huffman tables, so compressed_data,
+    compressed_size_bytes and compression_ratio differ from the host codec's; everything else is unchanged."""
     import concurrent.futures as cf
     import os as _os
-    from .core.compressor import encode_jpeg
+    from .core.compressor import encode_jpeg, encode_jpeg_batch
     from .core.precomputed_hilbert_index import PrecomputedIndex, _square_coordinates, PrecomputedLevel
     from ._dev import to_dev, to_np
     from . import kernels as K
 
+    if codec not in ("host", "device"):
+        raise ValueError(f"codec must be 'host' or 'device', got {codec!r}")
     sets = [np.array(p, dtype=np.float32) if isinstance(p, list) else p for p in parameter_sets]
     names = [model_ids[i] if model_ids else f"model_{i}" for i in range(len(sets))]
     descs = [descriptions[i] if descriptions else None for i in range(len(sets))]
@@ -268,8 +277,12 @@ def _ingest(hq: "HilbertQuantizer", parameter_sets, model_ids=None, descriptions
             frames, idx, mm = quantize_batch(X, hq.min_efficiency_ratio)
             n = int(frames.shape[2])
             pre = K.precomputed_index(X, n, 1) if hq.use_precomputed_indexing else None
-            fr_h, idx_h, mm_h = to_np(frames), to_np(idx), to_np(mm)
-            jpegs = list(pool.map(lambda k: encode_jpeg(fr_h[k], quality), range(len(members))))
+            idx_h, mm_h = to_np(idx), to_np(mm)
+            if codec == "device":
+                jpegs = encode_jpeg_batch(frames, quality)
+            else:
+                fr_h = to_np(frames)
+                jpegs = list(pool.map(lambda k: encode_jpeg(fr_h[k], quality), range(len(members))))
             pre_h = to_np(pre) if pre is not None else None
             layout = K.precomputed_layout(n) if pre is not None else None
             for k, i in enumerate(members):
@@ -314,12 +327,13 @@ class BatchQuantizer:
         self.logger = logging.getLogger(__name__)
 
     def quantize_batch(self, parameter_sets, model_ids: Optional[List[str]] = None,
-                       descriptions: Optional[List[str]] = None, parallel: bool = True) -> List[QuantizedModel]:
+                       descriptions: Optional[List[str]] = None, parallel: bool = True,
+                       codec: str = "host") -> List[QuantizedModel]:
         if model_ids and len(model_ids) != len(parameter_sets):
             raise ValueError("Number of model IDs must match number of parameter sets")
         if descriptions and len(descriptions) != len(parameter_sets):
             raise ValueError("Number of descriptions must match number of parameter sets")
-        return _ingest(self.quantizer, parameter_sets, model_ids, descriptions, parallel)
+        return _ingest(self.quantizer, parameter_sets, model_ids, descriptions, parallel, codec=codec)
 
     def search_batch(self, query_sets, candidate_models: List[QuantizedModel],
                      max_results: int = 10) -> List[List[SearchResult]]:

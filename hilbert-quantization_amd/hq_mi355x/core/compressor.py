@@ -5,12 +5,13 @@ semantics (core/compressor.py:256-303): a non-constant image stores (min, max) o
 constant image returns 128s and leaves the state untouched, and de-normalising without state is
 u8 / 255.  The arithmetic runs in hq_quantize_u8 / hq_dequantize_u8.  The JPEG ("MPEG-AI") codec
 after it is outside the hot path; `compress`/`decompress` wrap PIL on the host
-exactly where the reference does so the pipeline stays usable end to end.
+exactly where the reference does so the pipeline stays usable end to end.  `encode_jpeg_batch` is the batched
+ingest's opt-in device encoder (csrc/hq_jpeg.hip): valid baseline JPEGs, not PIL's bytes.
 """
 from __future__ import annotations
 
 import io
-from typing import Optional
+from typing import List, Optional
 
 import numpy as np
 
@@ -26,8 +27,24 @@ def encode_jpeg(u8: np.ndarray, quality: float) -> bytes:
     the same frame bytes give the same JPEG bytes as the per-model path."""
     from PIL import Image
     buf = io.BytesIO()
-    Image.fromarray(u8, "L").save(buf, format="JPEG", quality=max(1, min(95, int(quality * 95))), optimize=True)
+    Image.fromarray(u8, "L").save(buf, format="JPEG", quality=jpeg_quality(quality), optimize=True)
     return buf.getvalue()
+
+
+def jpeg_quality(quality: float) -> int:
+    """The reference's 0..1 quality as the libjpeg quality encode_jpeg passes to PIL."""
+    return max(1, min(95, int(quality * 95)))
+
+
+def encode_jpeg_batch(frames, quality: float) -> List[bytes]:
+    """The JPEG stage for a batch of normalised uint8 frames [N, H, W] (device tensor or ndarray) on the device
+    (kernels.jpeg_encode): one baseline JPEG per frame with encode_jpeg's quantisation table and the standard
+    Huffman tables, so not its bytes; decode_jpeg reads it.  The payloads come back in one copy (plus their
+    N + 1 offsets) and are sliced on the host."""
+    payload, offsets = K.jpeg_encode(to_dev(frames) if isinstance(frames, np.ndarray) else frames,
+                                     jpeg_quality(quality), CompressionError)
+    data, offs = to_np(payload), to_np(offsets)
+    return [data[offs[i]:offs[i + 1]].tobytes() for i in range(len(offs) - 1)]
 
 
 def check_payload(compressed_data) -> None:

@@ -1679,3 +1679,52 @@ def order_insert(S, exc=None):
     score = t.full((Q,), -1.0, dtype=t.float64, device=S2.device)
     _chk(_L().hq_order_insert(ptr(S2), N, Q, N, ptr(pos), ptr(score), stream()), exc)
     return pos, score
+
+
+# ------------------------------------------------------------------- batched JPEG encoder (hq_jpeg.hip)
+
+
+def _jpeg_frames(frames_u8):
+    t = torch()
+    if frames_u8.dtype != t.uint8:
+        raise TypeError(f"the JPEG encoder takes uint8 frames, got {frames_u8.dtype}")
+    fr = frames_u8.unsqueeze(0) if frames_u8.dim() == 2 else frames_u8
+    if fr.dim() != 3:
+        raise ValueError("frames must be [N, H, W] (or one [H, W] frame)")
+    return _contig(fr)
+
+
+def jpeg_blocks(H: int, W: int) -> int:
+    """8 x 8 blocks of an H x W frame (edges extended to multiples of 8)."""
+    return ((H + 7) // 8) * ((W + 7) // 8)
+
+
+def jpeg_encode(frames_u8, q: int, exc=None):
+    """u8 frames [N, H, W] -> (payload u8 [total], offsets int64 [N + 1]): frame i's baseline JPEG is
+    payload[offsets[i]:offsets[i + 1]] (hq_jpeg_encode; q = libjpeg quality 1 .. 95).  Two launches of one kernel:
+    the first measures every payload, the prefix sum of the lengths places them, the second writes.  The total is
+    read back once to size the buffer."""
+    t = torch()
+    fr = _jpeg_frames(frames_u8)
+    N, H, W = (int(s) for s in fr.shape)
+    lengths = t.empty(N, dtype=t.int32, device=fr.device)
+    offsets = t.zeros(N + 1, dtype=t.int64, device=fr.device)
+    _chk(_L().hq_jpeg_encode(ptr(fr), N, H, W, int(q), None, ptr(lengths), None, None, stream()), exc)
+    if N == 0:
+        return t.empty(0, dtype=t.uint8, device=fr.device), offsets
+    t.cumsum(lengths, 0, dtype=t.int64, out=offsets[1:])
+    out = t.empty(int(offsets[-1]), dtype=t.uint8, device=fr.device)
+    _chk(_L().hq_jpeg_encode(ptr(fr), N, H, W, int(q), ptr(offsets), None, ptr(out), None, stream()), exc)
+    return out, offsets
+
+
+def jpeg_coefficients(frames_u8, q: int, exc=None):
+    """The encoder's quantised DCT coefficients -> int16 [N, blocks, 64], blocks in raster order, every block in
+    zigzag order (the measuring launch of hq_jpeg_encode with its coefficient output)."""
+    t = torch()
+    fr = _jpeg_frames(frames_u8)
+    N, H, W = (int(s) for s in fr.shape)
+    coefs = t.empty((N, jpeg_blocks(H, W), 64), dtype=t.int16, device=fr.device)
+    lengths = t.empty(N, dtype=t.int32, device=fr.device)
+    _chk(_L().hq_jpeg_encode(ptr(fr), N, H, W, int(q), None, ptr(lengths), None, ptr(coefs), stream()), exc)
+    return coefs

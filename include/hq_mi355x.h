@@ -908,6 +908,30 @@ int hq_order_pairs(const double* Z, const uint8_t* flags, const double* X, int64
                    const int64_t* order, double* pair_sims, double* stats, hq_stream_t stream);
 int hq_order_insert(const double* S, int64_t ldS, int Q, int64_t N, int64_t* pos, double* score, hq_stream_t stream);
 
+/* ---- batched grayscale baseline JPEG encoder (csrc/hq_jpeg.hip) --------------------------------------
+ * The device form of the ingest's JPEG stage (core/compressor.py:71-80 of the reference, PIL on the host).
+ * frames [N, H, W] u8, contiguous.  One payload per frame: SOI, one DQT (8-bit, table 0), SOF0 (precision 8,
+ *   one component, sampling 1 x 1), the two Annex K luminance DHT segments, SOS, one scan without restart
+ *   markers, EOI.  Not byte-identical to libjpeg (fixed Huffman tables, float DCT); any baseline decoder reads it.
+ * q: libjpeg quality 1 .. 95 (else HQ_E_UNSUPPORTED).  Table entry = clip((base * s + 50) / 100, 1, 255) over the
+ *   Annex K luminance table with s = 5000 / q below 50 and 200 - 2 q from 50 (integer arithmetic).
+ * Coefficients: 8 x 8 blocks in raster order, the frame extended by its last row and column to multiples of 8,
+ *   level shift -128, orthonormal DCT-II in float32 on the matrix cores, true division by the table entry, round
+ *   to nearest (ties to even), DC clamped to [-1024, 1023], AC to +-1023.
+ * Two launches give a compact buffer without waits between workgroups:
+ *   out == NULL: lengths [N] int32 receives every payload's byte length (nothing else is written);
+ *   out != NULL: offsets [N + 1] int64 (offsets[0] = 0, the exclusive prefix sum of those lengths) places payload
+ *     i at out + offsets[i]; lengths may be NULL.  A frame whose length differs from offsets[i + 1] - offsets[i] is
+ *     not written (its lengths entry, when given, becomes -1): offsets must come from the same frames and q.
+ * coefs, when non-NULL (either launch): [N, blocks, 64] int16 quantised coefficients in zigzag order, blocks =
+ *   ceil(H / 8) * ceil(W / 8); 8-byte aligned.
+ * A frame needs 1408 + 4 (blocks + 1) + 336 blocks + 16 bytes of LDS (tables, coefficients and the worst-case
+ *   bit stream of 1658 bits per block): at most 477 blocks, e.g. 168 x 176; larger frames are HQ_E_UNSUPPORTED.
+ * N == 0 returns HQ_OK without a launch; a NULL frames, a NULL lengths with a NULL out, or a NULL offsets with a
+ *   non-NULL out is HQ_E_INVALID.                                                                             */
+int hq_jpeg_encode(const uint8_t* frames, int64_t N, int H, int W, int q, const int64_t* offsets, int32_t* lengths,
+                   uint8_t* out, int16_t* coefs, hq_stream_t stream);
+
 /* ---- §8e: the sharded search's one collective (RCCL over xGMI) ----------------------------------
  * The corpus is split into contiguous global-id ranges, one per GPU (one process per GPU); each rank
  * answers the whole query batch against its shard and packs fixed-size top-k records, and ONE
