@@ -13,6 +13,7 @@ stable-sorts those survivors by the overall score.
 from __future__ import annotations
 
 import threading
+import weakref
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -37,7 +38,7 @@ _FUSED_FINAL = True  # long lists: the final ranking inside the re-rank's sort (
 # store of each query's redo flag (5.5M -> 5.2M).  So did the copy queued at submit on a side stream that waits
 # for the re-rank's event (5.82-5.83M -> 5.67-5.69M at three batches in flight).
 _COUNT_READ = "copy"
-_RING = 16  # redo counters per (device, stream, thread): a slot is re-cleared _RING - 1 batches later
+_RING = 16  # redo counters per thread and (device, stream): a slot is re-cleared _RING - 1 batches later
 
 
 @dataclass
@@ -113,10 +114,154 @@ _REDO_WARM = False  # IndexCorpus._warm_redo ran in this process
 _WARM_LOCK = threading.Lock()
 
 
-def _lock(obj):
-    """The object's lock (created on first use; dict.setdefault is atomic under the GIL)."""
-    lk = obj.__dict__.get("_lock_")
-    return lk if lk is not None else obj.__dict__.setdefault("_lock_", threading.RLock())
+class _RedoRing:
+    """_RING device redo counters (`buf`, int32) used in turn by ONE thread on one stream: the exact re-rank
+    counts a batch's queries needing the dense path in its slot (zero on entry) and clears the following
+    batch's slot (hq_refine_rescore_topk_pp: no memset launch per batch), so a slot is cleared again
+    _RING - 1 batches later.  `unread[i]`: the side-read batch whose count still sits in slot i."""
+
+    __slots__ = ("buf", "next", "unread", "__weakref__")
+
+    def __init__(self, buf):
+        self.buf, self.next, self.unread = buf, 0, [None] * _RING
+
+    def take(self):
+        """(i, j, old): this batch's slot, the slot its re-rank clears, and the batch still unread in slot j
+        (or None) — the caller reads that one first.  Called with the state's lock held."""
+        i = self.next
+        j = self.next = (i + 1) % _RING
+        return i, j, self.unread[j]
+
+
+class _SideRead:
+    """One thread's side stream and one-element pinned buffer on a device (IndexCorpus._side_read)."""
+
+    __slots__ = ("stream", "host", "__weakref__")
+
+    def __init__(self, pair):
+        self.stream, self.host = pair
+
+
+class _PerThread(threading.local):
+    """A thread's part of a SearchState (made on the thread's first use, dropped when the thread ends): its
+    rings by (device, stream) and its side-read entries by device."""
+
+    def __init__(self):
+        self.rings, self.sides = {}, {}
+
+
+class SearchState:
+    """Everything an IndexCorpus keeps on the host between progressive batches, declared here and nowhere else.
+
+    Per corpus, behind `lock`, for the corpus's lifetime: the count of submitted batches not yet finished
+    (`pending`, the writer rule), the statistics (`counters`, `dense_s`, and `open_events`: the timing-event pairs
+    of redos still running), the free pinned one-element buffers per dtype, the adapted first-pass list
+    lengths (`slack`) and the constant fallback slots (`nofb`).
+
+    Per thread, in a threading.local: the thread's counter rings by (device, stream) and its side-read entry by
+    device.  They end with the thread — unless a submitted batch still refers to its ring, which then lives as
+    long as that batch — so a thread that gets a dead thread's ident starts with nothing.
+
+    The state allocates nothing itself: rings, side entries, pinned buffers and fallback slots are made by
+    the `make` argument of the call that misses them, events come from the caller."""
+
+    KEYS = ("batches", "queries", "redo_batches", "redo_queries", "retry_queries", "dense_queries")
+
+    def __init__(self):
+        self.lock = threading.RLock()
+        self.pending = 0
+        self.counters = dict.fromkeys(self.KEYS, 0)
+        self.dense_s = 0.0
+        self.open_events = []
+        self.pinned_free = {}
+        self.slack = {}
+        self.nofb = {}
+        self._tls = _PerThread()
+        self._rings, self._sides = weakref.WeakSet(), weakref.WeakSet()
+
+    def _mine(self, cache, live, key, cls, make):
+        ent = cache.get(key)
+        if ent is None:
+            ent = cache[key] = cls(make())
+            with self.lock:
+                live.add(ent)
+        return ent
+
+    def ring(self, key, make) -> _RedoRing:
+        """The calling thread's ring for key = (device, stream); make() -> its _RING-counter buffer, zeroed."""
+        return self._mine(self._tls.rings, self._rings, key, _RedoRing, make)
+
+    def side(self, key, make) -> _SideRead:
+        """The calling thread's side-read entry for the device `key`; make() -> (stream, pinned buffer)."""
+        return self._mine(self._tls.sides, self._sides, key, _SideRead, make)
+
+    def live(self) -> Tuple[int, int]:
+        """(rings, side entries) alive in any thread or held by a batch (weak references: for tests)."""
+        with self.lock:
+            return len(self._rings), len(self._sides)
+
+    def bump(self, events=None, **counts):
+        """Add to the counters; events: a redo's (start, end) timing pair, kept open until its end has
+        completed — with it, every open pair that has is folded into dense_s, so the list holds only the
+        redos still running."""
+        with self.lock:
+            for key, v in counts.items():
+                self.counters[key] += v
+            if events is not None:
+                pairs, self.open_events = self.open_events + [events], []
+                for e0, e1 in pairs:
+                    if e1.query():
+                        self.dense_s += e0.elapsed_time(e1) / 1e3
+                    else:
+                        self.open_events.append((e0, e1))
+
+    def stats(self) -> dict:
+        """A snapshot of the counters and dense_s, after waiting for the pairs still open."""
+        with self.lock:
+            done, self.open_events = self.open_events, []
+        dt = 0.0
+        for e0, e1 in done:
+            e1.synchronize()
+            dt += e0.elapsed_time(e1) / 1e3
+        with self.lock:
+            self.dense_s += dt
+            return dict(self.counters, dense_s=self.dense_s)
+
+    def reset_stats(self):
+        with self.lock:
+            self.counters = dict.fromkeys(self.KEYS, 0)
+            self.dense_s, self.open_events = 0.0, []
+
+    def pinned(self, dtype, make):
+        """A one-element pinned host buffer of `dtype`: a returned one, else make()."""
+        with self.lock:
+            free = self.pinned_free.get(dtype)
+            if free:
+                return free.pop()
+        return make()
+
+    def unpin(self, buf):
+        with self.lock:
+            self.pinned_free.setdefault(buf.dtype, []).append(buf)
+
+    def fallback(self, key, make):
+        with self.lock:
+            ent = self.nofb.get(key)
+            if ent is None:
+                ent = self.nofb[key] = make()
+            return ent
+
+    def slack_for(self, M: int, default: int) -> int:
+        with self.lock:
+            return self.slack.get(int(M), default)
+
+    def adapt(self, M: int, slack: int):
+        with self.lock:
+            self.slack[int(M)] = slack
+
+    def reset_list_lengths(self):
+        with self.lock:
+            self.slack.clear()
 
 
 class PendingSearch:
@@ -132,7 +277,7 @@ class PendingSearch:
         self.done, self.qp, self.out, self.res, self.cnt, self.forced = done, qp, out, res, cnt, forced
         self.nredo, self.event, self.threshold, self.M, self.K_out = nredo, event, threshold, M, K_out
         self.kp = kp  # the first pass's list length (the retry's base)
-        self.ring = ring  # side reads: (ring entry, slot) of the batch's device counter
+        self.ring = ring  # side reads: (_RedoRing, slot) of the batch's device counter
         self.counted = False  # in the corpus's count of unfinished batches (IndexCorpus.append's writer rule)
 
 
@@ -148,8 +293,9 @@ class IndexCorpus(ResidentRows):
 
     Re-entrant: the reference calls its engines from ThreadPoolExecutor workers (core/video_search.py:806,
     854; core/streaming_processor.py:294), so one corpus may serve many threads at once.  Every piece of
-    per-call device state (scan / re-rank workspace, redo counters) is keyed by thread as well as stream,
-    and the host-side caches (pinned buffers, statistics, adaptive list lengths) are guarded by a lock.
+    per-call device state (scan / re-rank workspace, redo counters, side stream) is thread-local, per stream,
+    and ends with its thread; the host-side caches (pinned buffers, statistics, adaptive list lengths) are
+    guarded by a lock.  All of it is declared in one place: SearchState, one per corpus (`_state`).
 
     Appendable: `append` writes new rows behind the resident ones (one hq_seg_append launch; nothing resident
     moves, the buffers grow geometrically) and `reserve` sizes the buffers ahead of time.  Both are WRITERS:
@@ -173,24 +319,34 @@ class IndexCorpus(ResidentRows):
         x = _f64(indices)
         if x.dim() != 2:
             raise ValueError("IndexCorpus expects a 2-D [N, L] array of index vectors")
-        self.N, self.L = int(x.shape[0]), int(x.shape[1])
-        self.id_base = int(id_base)
-        self.prep = K.flag_rows(K.packov(K.pack0(K.seg_prepare(x, src_f32=f32, row_f32=None if f32 else row_f32))))
-        self.nseg = self.prep.nseg
+        prep = K.flag_rows(K.packov(K.pack0(K.seg_prepare(x, src_f32=f32, row_f32=None if f32 else row_f32))))
+        self._adopt(prep, int(x.shape[1]), id_base)
+        self._warm_redo(x)
+
+    def _adopt(self, prep, L: int, id_base: int):
+        """Every field of a corpus over the prepared rows `prep` (the constructor's and select's one path)."""
+        self.N, self.L, self.id_base = prep.N, int(L), int(id_base)
+        self.prep, self.nseg = prep, prep.nseg
         # float32 rows outside the scans' model (values whose squares under/overflow in float32): the
         # whole corpus then takes the dense exact path (one host sync, at build time, f32 corpora only)
-        self.dense_only = bool(self.prep.unsafe_rows().any()) if self.prep.f32 and self.N else False
+        self.dense_only = bool(prep.unsafe_rows().any()) if prep.f32 and prep.N else False
+        self._state = SearchState()
         # the prepared layouts are written on the building thread's stream: a search on another stream waits
         # for them (an event wait queued on the device, no host sync)
-        self._pending = 0  # submitted progressive batches not yet finished (the writer rule)
         self._mark_ready()
-        self._warm_redo(x)
+
+    @classmethod
+    def _of_prep(cls, prep, L: int, id_base: int) -> "IndexCorpus":
+        c = cls.__new__(cls)
+        c._adopt(prep, L, id_base)
+        return c
 
     def _writer(self, what: str):
         """Entry of a writer (append / reserve): no submitted batch unfinished; ordered after the last writer."""
-        with _lock(self):
-            if self._pending:
-                raise RuntimeError(f"IndexCorpus.{what} with {self._pending} submitted search batch(es) unfinished: "
+        st = self._state
+        with st.lock:
+            if st.pending:
+                raise RuntimeError(f"IndexCorpus.{what} with {st.pending} submitted search batch(es) unfinished: "
                                    "call progressive_finish first")
         self._wait_ready()
 
@@ -310,13 +466,7 @@ class IndexCorpus(ResidentRows):
         sel = self._local_rows(rows, "select")
         self._wait_ready()
         prep = K.seg_gather(self.prep, sel, cap=max(1, sel.size), checked=True)
-        c = object.__new__(IndexCorpus)
-        c.N, c.L, c.id_base = prep.N, self.L, int(id_base)
-        c.prep, c.nseg = prep, prep.nseg
-        c.dense_only = bool(prep.unsafe_rows().any()) if prep.f32 and prep.N else False
-        c._pending = 0
-        c._mark_ready()
-        return c
+        return IndexCorpus._of_prep(prep, self.L, id_base)
 
     def _warm_redo(self, x):
         """Once per process, with the first corpus built: one 1-query progressive batch whose list is marked
@@ -495,7 +645,7 @@ class IndexCorpus(ResidentRows):
                     keep[t.nonzero(try_).view(-1)[ok]] = False
                     sel = sel[keep]
         if sel.numel():
-            self._bump(dense_queries=int(sel.numel()))
+            self._state.bump(dense_queries=int(sel.numel()))
             s2, i2, b2, bi2 = self._dense(qp, sel, mode, k, thr, thr_mode)
             sc[sel] = s2
             ids[sel] = i2
@@ -528,7 +678,7 @@ class IndexCorpus(ResidentRows):
         kp2 = self._retry_len(mode, cur)
         if kp2 is None:
             return None
-        self._bump(retry_queries=qp.N)
+        self._state.bump(retry_queries=qp.N)
         lo_mode = 0 if thr_mode == 0 else 1
         asc, aid, _, _ = K.scan_topk(qp, self.prep, mode, kp2, thr - self.EPS, lo_mode, self.id_base)
         tm = thr_mode | (K.THR_KEY32 if self.key32(qp) else 0)
@@ -571,11 +721,10 @@ class IndexCorpus(ResidentRows):
                     # the longer list resolved most of them: later batches at this M take the retry's list
                     # length on the first pass (one scan instead of a scan plus a retry per batch; results are
                     # exact either way).  Only when a retry ran: the scans without one keep their length.
-                    with _lock(self):
-                        self.__dict__.setdefault("_slack", {})[int(M)] = self._retry_len(0, cur) - M
+                    self._state.adapt(M, self._retry_len(0, cur) - M)
         d = t.nonzero(need).view(-1)
         if d.numel():
-            self._bump(dense_queries=int(d.numel()))
+            self._state.bump(dense_queries=int(d.numel()))
             dsel = sel[d]
             sub = qp.rows(dsel)
             s3, i3, b3, bi3 = self._dense(qp, dsel, 0, M, thr, 1)
@@ -635,8 +784,8 @@ class IndexCorpus(ResidentRows):
             ev.record()
             p = PendingSearch(qp=qp, out=(oid, odet, ocnt), res=res, cnt=cnt, forced=forced, nredo=nredo,
                               event=ev, threshold=float(threshold), M=M, K_out=K_out, kp=kp, ring=ring)
-            with _lock(self):
-                ring[0][2][ring[1]] = p
+            with self._state.lock:
+                ring[0].unread[ring[1]] = p
             return self._count(p)
         # the counter's value leaves now, behind the re-rank (a last-workgroup write of it to the pinned int from
         # the re-rank kernel measured slower: 21 -> 43 us, every workgroup's release fence)
@@ -649,16 +798,18 @@ class IndexCorpus(ResidentRows):
 
     def _count(self, p: "PendingSearch") -> "PendingSearch":
         """A batch left unfinished by progressive_submit: counted until progressive_finish (the writer rule)."""
-        with _lock(self):
-            self._pending += 1
+        st = self._state
+        with st.lock:
+            st.pending += 1
             p.counted = True
         return p
 
     def _uncount(self, p: "PendingSearch"):
-        with _lock(self):
+        st = self._state
+        with st.lock:
             if p.counted:
                 p.counted = False
-                self._pending -= 1
+                st.pending -= 1
 
     def progressive_finish(self, p: "PendingSearch"):
         """Wait for a submitted batch's redo count (the one host sync) and recompute the queries whose
@@ -679,7 +830,7 @@ class IndexCorpus(ResidentRows):
             p.event.synchronize()
             nredo = int(p.nredo[0])
             self._unpin(p.nredo)  # read: reusable
-        self._bump(batches=1, queries=p.qp.N)
+        self._state.bump(batches=1, queries=p.qp.N)
         if nredo > 0:
             # the redo's time on the stream, between two events read lazily (stats): no host sync here, so the
             # host goes on queueing batches while the redo runs
@@ -697,11 +848,9 @@ class IndexCorpus(ResidentRows):
                 oid[sel], odet[sel], ocnt[sel] = o2, dd2, c2
             e1 = t.cuda.Event(enable_timing=True)
             e1.record()
-            self._bump(redo_batches=1, redo_queries=n, _events=(e0, e1))
+            self._state.bump(redo_batches=1, redo_queries=n, events=(e0, e1))
         p.done = (oid, odet[..., 0], odet[..., 1:], ocnt)  # finishing again returns the same results
         return p.done
-
-    _STAT_KEYS = ("batches", "queries", "redo_batches", "redo_queries", "retry_queries", "dense_queries")
 
     @property
     def stats(self) -> dict:
@@ -710,121 +859,79 @@ class IndexCorpus(ResidentRows):
         stream time spent there (dense_s: between two events around each redo, read here — this waits for
         the redos still running); of the redone queries, those re-scanned with a longer list (retry_queries)
         and those scored densely (dense_queries).  A snapshot: later batches do not change it."""
-        with _lock(self):
-            st = self.__dict__.setdefault("_stats", dict.fromkeys(self._STAT_KEYS, 0))
-            evs = self.__dict__.setdefault("_stat_events", [])
-            done, evs[:] = list(evs), []
-            st["dense_s"] = st.get("dense_s", 0.0)
-        dt = 0.0
-        for e0, e1 in done:
-            e1.synchronize()
-            dt += e0.elapsed_time(e1) / 1e3
-        with _lock(self):
-            st["dense_s"] += dt
-            return dict(st)
-
-    def _bump(self, _events=None, **counts):
-        with _lock(self):
-            st = self.__dict__.setdefault("_stats", dict.fromkeys(self._STAT_KEYS, 0))
-            for key, v in counts.items():
-                st[key] += v
-            if _events is not None:
-                self.__dict__.setdefault("_stat_events", []).append(_events)
+        return self._state.stats()
 
     def reset_stats(self):
-        with _lock(self):
-            self.__dict__.pop("_stats", None)
-            self.__dict__.pop("_stat_events", None)
+        self._state.reset_stats()
 
     def _pinned(self, dtype):
         """A one-element pinned host buffer: recycled once its batch is finished (a fresh pinned
         allocation per batch can stall the host between launches)."""
-        with _lock(self):
-            free = self.__dict__.setdefault("_pinned_free", {}).setdefault(dtype, [])
-            if free:
-                return free.pop()
-        return torch().empty(1, dtype=dtype, pin_memory=True)
+        return self._state.pinned(dtype, lambda: torch().empty(1, dtype=dtype, pin_memory=True))
 
     def _unpin(self, buf):
         """Return a pinned buffer whose value has been read."""
-        with _lock(self):
-            self.__dict__.setdefault("_pinned_free", {}).setdefault(buf.dtype, []).append(buf)
+        self._state.unpin(buf)
 
     def _redo_counter(self, dev, side: bool = False):
-        """(counter, next, ring): device int32 [1] views of a ring of _RING counters used in turn by ONE thread
-        on one stream — the exact re-rank counts this batch's queries needing the dense path in `counter`
-        (zero on entry) and clears `next`, the following batch's counter (hq_refine_rescore_topk_pp: no memset
-        launch per batch), so a slot is cleared again _RING - 1 batches later; ring[2] counts the batches whose
-        slot is still to be read (progressive_finish).  Keyed by thread too: two threads sharing a stream would
-        otherwise take slots of one ring and clear each other's count before it is read."""
+        """(counter, next, ring): device int32 [1] views of two slots of the calling thread's _RedoRing for
+        this stream — the exact re-rank counts this batch's queries needing the dense path in `counter` and
+        clears `next`, the following batch's — and, for a side read, (the ring, the slot).  Per thread: two
+        threads sharing a stream would otherwise take slots of one ring and clear each other's count before
+        it is read."""
         t = torch()
-        key = (str(dev), K.stream(), threading.get_ident())
-        with _lock(self):
-            cache = self.__dict__.setdefault("_redo", {})
-            ent = cache.get(key)
-            if ent is None:
-                ent = cache[key] = [t.zeros(_RING, dtype=t.int32, device=dev), 0, [None] * _RING]
-            buf, i = ent[0], ent[1]
-            ent[1] = (i + 1) % _RING
-            j = (i + 1) % _RING
-            old = ent[2][j]  # a batch still unread whose slot this batch's re-rank clears: read it first
+        st = self._state
+        ring = st.ring((str(dev), K.stream()), lambda: t.zeros(_RING, dtype=t.int32, device=dev))
+        with st.lock:
+            i, j, old = ring.take()
         if old is not None:
             self._resolve(old)
-        return buf[i:i + 1], buf[j:j + 1], ((ent, i) if side else None)
+        return ring.buf[i:i + 1], ring.buf[j:j + 1], ((ring, i) if side else None)
 
     def _resolve(self, p) -> int:
         """A side-read batch's redo count (once): wait for its event, read its slot, free the slot."""
-        with _lock(self):
+        st = self._state
+        with st.lock:
             if isinstance(p.nredo, int):
                 return p.nredo
         p.event.synchronize()
         v = self._side_read(p.nredo)
-        with _lock(self):
+        with st.lock:
             if not isinstance(p.nredo, int):
-                ent, i = p.ring
-                if ent[2][i] is p:
-                    ent[2][i] = None
+                ring, i = p.ring
+                if ring.unread[i] is p:
+                    ring.unread[i] = None
                 p.nredo = v
         return v
 
     def _side_read(self, slot) -> int:
-        """The value of a finished batch's device counter, read on this thread's side stream (the search
-        stream goes on with the next batch's kernels; no copy is queued on it)."""
+        """The value of a finished batch's device counter, read on the calling thread's side stream (the
+        search stream goes on with the next batch's kernels; no copy is queued on it)."""
         t = torch()
-        key = (slot.device.index, threading.get_ident())
-        with _lock(self):
-            ss = self.__dict__.setdefault("_side", {})
-            st = ss.get(key)
-            if st is None:
-                st = ss[key] = (t.cuda.Stream(device=slot.device), t.empty(1, dtype=slot.dtype, pin_memory=True))
-        side, host = st
-        with t.cuda.stream(side):
-            host.copy_(slot, non_blocking=True)
-        side.synchronize()
-        return int(host[0])
+        s = self._state.side(slot.device.index, lambda: (t.cuda.Stream(device=slot.device),
+                                                         t.empty(1, dtype=slot.dtype, pin_memory=True)))
+        with t.cuda.stream(s.stream):
+            s.host.copy_(slot, non_blocking=True)
+        s.stream.synchronize()
+        return int(s.host[0])
 
     def _no_fallback(self, Q: int, dev):
         """Constant (-inf, -1, zeros) fallback slot of a batch of Q queries, cached per stream: the fills
         are stream-ordered, so a batch on another stream must not read them before they ran."""
         t = torch()
-        cache = self.__dict__.setdefault("_nofb", {})
-        key = (Q, str(dev), K.stream())
-        if key not in cache:
-            cache[key] = (t.full((Q,), -float("inf"), dtype=t.float64, device=dev),
-                          t.full((Q,), -1, dtype=t.int64, device=dev),
-                          t.zeros((Q, 1 + self.nseg), dtype=t.float64, device=dev))
-        return cache[key]
+        return self._state.fallback((Q, str(dev), K.stream()), lambda: (
+            t.full((Q,), -float("inf"), dtype=t.float64, device=dev),
+            t.full((Q,), -1, dtype=t.int64, device=dev),
+            t.zeros((Q, 1 + self.nseg), dtype=t.float64, device=dev)))
 
     def reset_list_lengths(self):
         """Forget the first-pass list lengths the corpus adapted (slack_for): back to SLACK at every M."""
-        with _lock(self):
-            self.__dict__.pop("_slack", None)
+        self._state.reset_list_lengths()
 
     def slack_for(self, M: int) -> int:
         """Extra list entries of the first pass at list length M: SLACK, or the longer list a corpus with
         runs of near-duplicates showed it needs (_level0_redo: most lists of a batch ended in near-ties)."""
-        with _lock(self):
-            return self.__dict__.get("_slack", {}).get(int(M), self.SLACK)
+        return self._state.slack_for(M, self.SLACK)
 
     def _scan_refine(self, qp, mode: int, k: int, thr: float, thr_mode: int, nredo=None, det: bool = False,
                      next_redo=None, slack=None):
@@ -913,6 +1020,7 @@ class ProgressiveSimilaritySearchEngine(*_bases("interfaces", "SimilaritySearchE
     def __init__(self, similarity_threshold: float = 0.1, max_candidates_per_level: int = 100):
         self.similarity_threshold = similarity_threshold
         self.max_candidates_per_level = max_candidates_per_level
+        self._lock = threading.RLock()  # the pool cache and its counters
         # [index arrays of the last uniform pool, their resident IndexCorpus, searches using it right now]
         self._pool_cache = None
         self._pool_stats = {"builds": 0, "appends": 0}
@@ -921,13 +1029,13 @@ class ProgressiveSimilaritySearchEngine(*_bases("interfaces", "SimilaritySearchE
     @property
     def pool_stats(self) -> Dict[str, int]:
         """How the resident pool corpus came about so far: full builds, and appends of a pool's new tail."""
-        with _lock(self):
+        with self._lock:
             return dict(self._pool_stats)
 
     @property
     def pool_shrinks(self) -> int:
         """Removals applied to the resident pool corpus in place of a rebuild (shrink_resident)."""
-        with _lock(self):
+        with self._lock:
             return self._pool_shrinks
 
     # ---- structure -----------------------------------------------------------------------------
@@ -961,14 +1069,14 @@ class ProgressiveSimilaritySearchEngine(*_bases("interfaces", "SimilaritySearchE
         using that corpus right now (append is a writer): then a fresh corpus is built, as for any other
         pool.  Every acquire is paired with a _pool_release once the caller's search has finished."""
         arrays = [c.hierarchical_indices for c in pool]
-        with _lock(self):  # threads searching one pool share one resident corpus (built once)
+        with self._lock:  # threads searching one pool share one resident corpus (built once)
             hit = self._pool_cache
             n = len(hit[0]) if hit is not None else 0
             if hit is not None and n <= len(arrays) and all(a is b for a, b in zip(hit[0], arrays)):
                 if n == len(arrays):
                     hit[2] += 1
                     return hit[1]
-                if hit[2] == 0 and hit[1]._pending == 0:
+                if hit[2] == 0 and hit[1]._state.pending == 0:
                     tail = arrays[n:]
                     flags = np.array([_is_f32(r) for r in tail], dtype=bool)
                     hit[1].append(np.stack([np.asarray(r, dtype=np.float64) for r in tail]), row_f32=flags)
@@ -976,7 +1084,7 @@ class ProgressiveSimilaritySearchEngine(*_bases("interfaces", "SimilaritySearchE
                     hit[2] += 1
                     self._pool_stats["appends"] += 1
                     return hit[1]
-            elif hit is not None and self.shrink_resident and hit[2] == 0 and hit[1]._pending == 0:
+            elif hit is not None and self.shrink_resident and hit[2] == 0 and hit[1]._state.pending == 0:
                 diff = _pool_diff(hit[0], arrays)
                 if diff is not None:
                     kept, t0 = diff
@@ -999,7 +1107,7 @@ class ProgressiveSimilaritySearchEngine(*_bases("interfaces", "SimilaritySearchE
             return corpus
 
     def _pool_release(self, corpus: IndexCorpus):
-        with _lock(self):
+        with self._lock:
             hit = self._pool_cache
             if hit is not None and hit[1] is corpus:
                 hit[2] -= 1

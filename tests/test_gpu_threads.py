@@ -22,7 +22,7 @@ def _np(x):
     return to_np(x)
 
 
-def _indices(seed, clustered):
+def _indices(seed, clustered, NB=NB, RUN=RUN):
     """[NB * RUN, 64] f64 index vectors (the fused map + index kernel on random 1536-D embeddings) and 48
     queries; clustered: NB base vectors repeated in runs of RUN + N(0, 0.01), queries drawn from the runs."""
     import torch
@@ -33,7 +33,8 @@ def _indices(seed, clustered):
     if clustered:
         C = B.repeat_interleave(RUN, 0)
         C.add_(0.01 * torch.randn(C.shape, generator=g, device="cuda", dtype=torch.float64))
-        Q = B[:48] + 0.01 * torch.randn((48, 64), generator=g, device="cuda", dtype=torch.float64)
+        Q = B[torch.arange(48, device="cuda") % NB] + 0.01 * torch.randn((48, 64), generator=g, device="cuda",
+                                                                          dtype=torch.float64)
     else:
         C = B
         Q = B[::(NB * RUN) // 48][:48] + 0.01 * torch.randn((48, 64), generator=g, device="cuda",
@@ -132,3 +133,133 @@ def test_corpus_batches_threads_equal_serial(hq_lib, M, own_stream):
     assert st["batches"] == 2 * len(Qb)
     if M == 20:
         assert st["retry_queries"] > 0, st  # the longer-list retry ran inside the threads
+
+
+# ---- short-lived threads, selected corpora, timing events: the corpus's host state (SearchState) ----------------
+# The smallest clustered corpus that still takes the fused level-0 scan: 32 runs of 64 near-duplicates (2,048 rows;
+# N > M, and a list of M + SLACK entries ends inside a run), three batches of 16 queries at M = 20, no list
+# adaptation (every batch then behaves the same, however often it ran before).
+SMALL_NB, SMALL_M = 32, 20
+_COUNTERS = ("batches", "queries", "redo_queries", "retry_queries", "dense_queries")
+
+
+def _small_corpus(C, mode=None):
+    from hq_mi355x.core.search_engine import IndexCorpus
+    corpus = IndexCorpus(C)
+    corpus.ADAPT_LISTS = False
+    if mode is not None:
+        corpus._count_read = mode
+    corpus.reset_stats()
+    return corpus
+
+
+def _prog(corpus, q):
+    return [_np(x) for x in corpus.progressive(q, 10, 0.1, SMALL_M)]
+
+
+@pytest.fixture(scope="module")
+def small(hq_lib):
+    """(C, the three query batches on the device, each batch's serial results, each batch's serial counters)."""
+    import torch
+    C, Q = _indices(17, True, NB=SMALL_NB)
+    Qb = [torch.from_numpy(Q[i:i + 16]).cuda() for i in range(0, 48, 16)]
+    torch.cuda.synchronize()
+    corpus = _small_corpus(C)
+    serial, counters = [], []
+    for q in Qb:
+        corpus.reset_stats()
+        serial.append(_prog(corpus, q))
+        counters.append(corpus.stats)
+    print(f"small clustered corpus {C.shape}, M={SMALL_M}: serial counters per batch {counters}")
+    return C, Qb, serial, counters
+
+
+@pytest.mark.parametrize("mode", ["copy", "side"])
+def test_short_lived_threads_equal_serial(small, mode):
+    """64 threads in 8 waves of 8, each searching one batch once and ending (the reference's per-call
+    ThreadPoolExecutor workers), half of them on a stream of their own: every result and the counters equal the
+    serial run's, and no ring, side stream or pinned side buffer of an ended thread is left in the corpus."""
+    import gc
+    import threading
+    import torch
+    C, Qb, serial, counters = small
+    corpus = _small_corpus(C, mode)
+    got = [None] * 64
+
+    def run(t):
+        try:
+            if t % 2:
+                s = torch.cuda.Stream()
+                with torch.cuda.stream(s):
+                    got[t] = _prog(corpus, Qb[t % 3])
+                s.synchronize()
+            else:
+                got[t] = _prog(corpus, Qb[t % 3])
+        except BaseException as e:  # reported by the main thread below
+            got[t] = e
+
+    for w in range(8):
+        ths = [threading.Thread(target=run, args=(8 * w + i,)) for i in range(8)]
+        for th in ths:
+            th.start()
+        for th in ths:
+            th.join()
+    for t in range(64):
+        assert not isinstance(got[t], BaseException), (t, got[t])
+        for x, y in zip(got[t], serial[t % 3]):
+            np.testing.assert_array_equal(x, y, err_msg=f"thread {t}")
+    st = corpus.stats
+    runs = [len(range(b, 64, 3)) for b in range(3)]
+    print(f"{mode}: redo path in the threads: {sum(r * c['redo_batches'] for r, c in zip(runs, counters))} batches; {st}")
+    for key in _COUNTERS:
+        assert st[key] == sum(r * c[key] for r, c in zip(runs, counters)), (key, st, counters)
+    del ths, th
+    torch.cuda.synchronize()
+    gc.collect()
+    rings, sides = corpus._state.live()
+    print(f"{mode}: live rings {rings}, side entries {sides}")
+    assert rings <= 1 and sides <= (1 if mode == "side" else 0)  # the main thread's own, at most
+
+
+def test_selected_corpus_is_a_full_corpus(small):
+    """select() builds its corpus the way the constructor does: the same answers as a fresh build of the rows,
+    statistics of its own, and the writer rule."""
+    C, Qb, _, _ = small
+    corpus = _small_corpus(C)
+    before = corpus.stats
+    c = corpus.select(range(0, len(C), 2))
+    c.ADAPT_LISTS = False
+    fresh = _small_corpus(np.ascontiguousarray(C[::2]))
+    for q in Qb:
+        for x, y in zip(_prog(c, q), _prog(fresh, q)):
+            np.testing.assert_array_equal(x, y)
+    cs, fs = c.stats, fresh.stats
+    assert [cs[k] for k in _COUNTERS] == [fs[k] for k in _COUNTERS] and cs["batches"] == 3
+    assert corpus.stats == before
+    for cc in (c, fresh):
+        p = cc.progressive_submit(Qb[0], 10, 0.1, SMALL_M)
+        assert p.done is None
+        with pytest.raises(RuntimeError, match="unfinished"):
+            cc.append(C[:1])
+        cc.progressive_finish(p)
+        assert cc.append(C[:1]) == len(C) // 2 + 1
+
+
+def test_open_timing_events_stay_bounded(small):
+    """51 redo batches with `stats` never read: the pairs of finished redos are folded as later redos arrive, so
+    one pair at most is open at the end, and nothing is lost from redo_batches or dense_s."""
+    import torch
+    C, Qb, _, counters = small
+    b = max(range(3), key=lambda i: counters[i]["redo_batches"])
+    assert counters[b]["redo_batches"] == 1, counters  # this test is about the redo path: it must run
+    corpus = _small_corpus(C)
+    for _ in range(50):
+        corpus.progressive_finish(corpus.progressive_submit(Qb[b], 10, 0.1, SMALL_M))
+    torch.cuda.synchronize()
+    corpus.progressive(Qb[b], 10, 0.1, SMALL_M)
+    nopen = len(corpus._state.open_events)
+    st = corpus.stats
+    print(f"open pairs after 51 redo batches: {nopen}; {st}")
+    assert nopen <= 1
+    assert st["redo_batches"] == 51 and st["redo_queries"] == 51 * counters[b]["redo_queries"]
+    assert st["dense_s"] > 0
