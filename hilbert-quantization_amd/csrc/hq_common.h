@@ -55,6 +55,7 @@ enum Opt {
   OPT_RANK_CT, OPT_RANK_WIN, OPT_RANK_SORT_NT, OPT_RANK_SORT_SMALL,
   OPT_DECODE_NT, OPT_DECODE_GENERIC,
   OPT_COS_TOPK_HINT,
+  OPT_JPEG_DECODE_F,
   OPT_COUNT
 };
 int64_t opt(Opt id, int64_t dflt);

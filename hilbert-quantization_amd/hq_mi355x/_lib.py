@@ -157,6 +157,8 @@ SIGNATURES = {
     "hq_order_pairs": (_i, [_p, _p, _p, _i64, _i64, _i, _p, _p, _p, _p]),
     "hq_order_insert": (_i, [_p, _i64, _i, _i64, _p, _p, _p]),
     "hq_jpeg_encode": (_i, [_p, _i64, _i, _i, _i, _p, _p, _p, _p, _p]),
+    "hq_jpeg_probe": (_i, [_p, _p, _i64, _p, _p]),
+    "hq_jpeg_decode": (_i, [_p, _p, _p, _p, _i64, _i, _i, _p, _p, _p, _p]),
 }
 
 _lock = threading.Lock()

@@ -150,12 +150,17 @@ class HilbertQuantizer:
         except Exception as e:
             raise ReconstructionError(f"Unexpected error during reconstruction: {e}") from e
 
-    def reconstruct_many(self, quantized_models: List[QuantizedModel], validate: bool = True) -> List[np.ndarray]:
+    def reconstruct_many(self, quantized_models: List[QuantizedModel], validate: bool = True,
+                         codec: str = "host") -> List[np.ndarray]:
         """reconstruct() for many models: host JPEG decode on threads, one fused de-normalise + inverse Hilbert
-        gather launch per frame shape (core.pipeline.reconstruct_batch); same arrays and errors."""
+        gather launch per frame shape (core.pipeline.reconstruct_batch); same arrays and errors.
+        codec="device" decodes the payloads on the GPU as well (hq_jpeg_decode: the same pixels, so the same
+        arrays); payloads it does not take fall to the host decoder one by one."""
         from .core.pipeline import reconstruct_batch
+        if codec not in ("host", "device"):
+            raise ValueError(f"codec must be 'host' or 'device', got {codec!r}")
         try:
-            out = reconstruct_batch(quantized_models, self.quantization_pipeline.compressor)
+            out = reconstruct_batch(quantized_models, self.quantization_pipeline.compressor, codec=codec)
             return [o if o is not None else self.reconstruct(m, validate) for o, m in zip(out, quantized_models)]
         except (ReconstructionError, ValidationError):
             raise
@@ -392,9 +397,9 @@ class BatchQuantizer:
             results[i] = [r for r in res if r.similarity_score >= thr]
         return results
 
-    def reconstruct_batch(self, quantized_models: List[QuantizedModel]) -> List[np.ndarray]:
+    def reconstruct_batch(self, quantized_models: List[QuantizedModel], codec: str = "host") -> List[np.ndarray]:
         """Batched reconstruct (HilbertQuantizer.reconstruct_many)."""
-        return self.quantizer.reconstruct_many(quantized_models)
+        return self.quantizer.reconstruct_many(quantized_models, codec=codec)
 
     def quantize_device(self, parameters, index_space_size: Optional[int] = None):
         """f32 [N, d] -> (frames u8 [N, n+1, n], indices f64 [N, L], minmax f32 [N, 2]) on the GPU."""

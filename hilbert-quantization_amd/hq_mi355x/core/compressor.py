@@ -6,7 +6,8 @@ constant image returns 128s and leaves the state untouched, and de-normalising w
 u8 / 255.  The arithmetic runs in hq_quantize_u8 / hq_dequantize_u8.  The JPEG ("MPEG-AI") codec
 after it is outside the hot path; `compress`/`decompress` wrap PIL on the host
 exactly where the reference does so the pipeline stays usable end to end.  `encode_jpeg_batch` is the batched
-ingest's opt-in device encoder (csrc/hq_jpeg.hip): valid baseline JPEGs, not PIL's bytes.
+ingest's opt-in device encoder (csrc/hq_jpeg.hip): valid baseline JPEGs, not PIL's bytes.  `decode_jpeg_batch` is
+the batched reconstruct's opt-in device decoder (csrc/hq_jpeg_decode.hip): PIL's pixels, bit for bit.
 """
 from __future__ import annotations
 
@@ -59,6 +60,42 @@ def decode_jpeg(compressed_data: bytes) -> np.ndarray:
     """Host JPEG decode of one payload -> uint8 frame (the reference's np.array(Image.open(...)) values)."""
     from PIL import Image
     return np.array(Image.open(io.BytesIO(compressed_data)), dtype=np.uint8)
+
+
+def decode_jpeg_batch(payloads):
+    """Decode a list of payloads on the device (kernels.jpeg_probe + kernels.jpeg_decode): one join, one upload, one
+    probe launch, then one decode launch per frame shape.  Returns (groups, refused): groups = [(frames u8 device
+    tensor [m, H, W], indices ndarray [m])] with frames[k] = PIL's pixels of payloads[indices[k]]; refused = the
+    indices (ascending) the device does not take (anything but a grayscale baseline JPEG without restart
+    intervals up to kernels.JPEG_MAX_WIDTH wide, a damaged one, something that is not bytes): they are the host
+    decoder's."""
+    import torch
+    data = [p if isinstance(p, bytes) else b"" for p in payloads]
+    N = len(data)
+    if N == 0:
+        return [], []
+    offs = np.zeros(N + 1, dtype=np.int64)
+    np.cumsum([len(p) for p in data], out=offs[1:])
+    joined = np.frombuffer(bytearray(b"".join(data) or b"\0"), dtype=np.uint8)  # writable: no copy in to_dev
+    payload, offsets = to_dev(joined), to_dev(offs)
+    desc = K.jpeg_probe(payload, offsets, CompressionError)
+    head = to_np(desc[:, :3])
+    ok = (head[:, 0] == 0) & (head[:, 2] <= K.JPEG_MAX_WIDTH)
+    shapes = {}
+    for i in np.flatnonzero(ok):
+        shapes.setdefault((int(head[i, 1]), int(head[i, 2])), []).append(int(i))
+    launched = [(ids, K.jpeg_decode(payload, offsets, desc, ids, H, W, exc=CompressionError))
+                for (H, W), ids in shapes.items()]
+    groups, refused = [], [int(i) for i in np.flatnonzero(~ok)]
+    for ids, (frames, status) in launched:
+        good = to_np(status) == 0
+        ids = np.asarray(ids, dtype=np.int64)
+        if not good.all():
+            refused.extend(int(i) for i in ids[~good])
+            frames, ids = frames[torch.from_numpy(np.flatnonzero(good)).to(frames.device)], ids[good]
+        if len(ids):
+            groups.append((frames, ids))
+    return groups, sorted(refused)
 
 
 class MPEGAICompressorImpl(*_bases("interfaces", "MPEGAICompressor")):

@@ -181,7 +181,7 @@ def extract_indices_batch(frames, minmax):
     return rows, lens
 
 
-def reconstruct_batch(models, compressor: MPEGAICompressorImpl, workers: int = 16):
+def reconstruct_batch(models, compressor: MPEGAICompressorImpl, workers: int = 16, codec: str = "host"):
     """Batched QuantizationPipeline.reconstruct_parameters (core/pipeline.py:183-235) for
     many QuantizedModels: the JPEG payloads decode on a host thread pool (the codec), then every group of
     (n + 1) x n frames takes ONE fused launch (hq_dequantize_unmap: de-normalise with the compressor
@@ -190,9 +190,16 @@ def reconstruct_batch(models, compressor: MPEGAICompressorImpl, workers: int = 1
     [members, d] floats; each model's vector is truncated to its own count.  Frames of another shape are
     left to the per-model path (None).  Returns float32 NumPy vectors in model order; the errors are the
     per-model path's (HilbertQuantizationError wrapping the decompress / shape failure of the first failing
-    model)."""
+    model).
+
+    codec="device": the payloads decode on the device (compressor.decode_jpeg_batch: PIL's pixels, bit for bit) and
+    their frames go to hq_dequantize_unmap where they are; only the payloads the device refuses take the host
+    decoder above, so the vectors, the errors and their order are those of codec="host"."""
     import concurrent.futures as cf
-    from .compressor import check_payload, decode_jpeg
+    import torch
+    from .compressor import check_payload, decode_jpeg, decode_jpeg_batch
+    if codec not in ("host", "device"):
+        raise ValueError(f"codec must be 'host' or 'device', got {codec!r}")
     models = list(models)
     out = [None] * len(models)
 
@@ -207,18 +214,34 @@ def reconstruct_batch(models, compressor: MPEGAICompressorImpl, workers: int = 1
         except Exception as e:
             raise HilbertQuantizationError(f"Failed to reconstruct parameters: {e}")
 
-    with cf.ThreadPoolExecutor(max_workers=max(1, min(workers, len(models) or 1))) as pool:
-        frames = list(pool.map(decode, range(len(models))))
+    # on_dev[i] = (device frames [m, H, W], row) for the payloads the device decoded; the others decode here
+    on_dev, todo = {}, range(len(models))
+    if codec == "device":
+        dev_groups, todo = decode_jpeg_batch([m.compressed_data for m in models])
+        for fr, ids in dev_groups:
+            on_dev.update((int(i), (fr, k)) for k, i in enumerate(ids))
+    with cf.ThreadPoolExecutor(max_workers=max(1, min(workers, len(todo) or 1))) as pool:
+        frames = dict(zip(todo, pool.map(decode, todo)))
     mm = to_dev(compressor._state_minmax())
     groups = {}
-    for i, f in enumerate(frames):
-        groups.setdefault(f.shape, []).append(i)
+    for i in range(len(models)):
+        groups.setdefault(tuple(on_dev[i][0].shape[1:]) if i in on_dev else frames[i].shape, []).append(i)
     for shape, members in groups.items():
         if len(shape) != 2 or shape[0] < 2 or shape[0] - 1 != shape[1] or (shape[1] & (shape[1] - 1)) != 0:
             continue  # not an (n + 1) x n enhanced frame: per-model path
         c = shape[1]
         d = min(max(max(int(models[i].parameter_count) for i in members), 0), c * c)
-        u8 = to_dev(np.stack([frames[i] for i in members]))
+        here = [i for i in members if i not in on_dev]
+        if len(here) == len(members):
+            u8 = to_dev(np.stack([frames[i] for i in members]))
+        else:  # one decode launch made this shape's device frames, in member order: a gather only around refusals
+            src, rows = on_dev[next(i for i in members if i in on_dev)][0], [on_dev[i][1] for i in members if i in on_dev]
+            u8 = src if not here and rows == list(range(src.shape[0])) else None
+            if u8 is None:
+                parts = torch.cat([src, to_dev(np.stack([frames[i] for i in here]))]) if here else src
+                at = {i: src.shape[0] + k for k, i in enumerate(here)}
+                pick = [on_dev[i][1] if i in on_dev else at[i] for i in members]
+                u8 = parts[torch.tensor(pick, dtype=torch.int64, device=parts.device)]
         if 2 <= c <= 128:
             flat = to_np(K.dequantize_unmap(u8, mm, d, exc=HilbertQuantizationError))
         else:  # sides the fused kernel does not take (1, above 128): de-normalise, then the generic gather

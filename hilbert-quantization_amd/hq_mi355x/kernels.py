@@ -1728,3 +1728,55 @@ def jpeg_coefficients(frames_u8, q: int, exc=None):
     lengths = t.empty(N, dtype=t.int32, device=fr.device)
     _chk(_L().hq_jpeg_encode(ptr(fr), N, H, W, int(q), None, ptr(lengths), None, ptr(coefs), stream()), exc)
     return coefs
+
+
+# ------------------------------------------------------------------- batched JPEG decoder (hq_jpeg_decode.hip)
+
+JPEG_DESC_WORDS = 8   # status, H, W, offsets of the DQT entries, the DC counts, the AC counts, the scan, unused
+JPEG_MAX_WIDTH = 224  # hq_jpeg_decode: wider frames are HQ_E_UNSUPPORTED
+
+
+def _jpeg_payload(payload, offsets):
+    t = torch()
+    if payload.dtype != t.uint8 or offsets.dtype != t.int64:
+        raise TypeError(f"the JPEG decoder takes a uint8 payload and int64 offsets, got {payload.dtype}, {offsets.dtype}")
+    if payload.dim() != 1 or offsets.dim() != 1 or offsets.numel() < 1:
+        raise ValueError("payload must be [total] and offsets [N + 1]")
+    return _contig(payload), _contig(offsets)
+
+
+def jpeg_probe(payload, offsets, exc=None):
+    """payload u8 [total], offsets int64 [N + 1] (payload i = payload[offsets[i]:offsets[i + 1]], offsets[-1] <=
+    total: the caller's contract) -> descriptors int32 [N, 8] (hq_jpeg_probe): status (0 = a grayscale baseline
+    JPEG the device decodes), H, W and the offsets hq_jpeg_decode needs."""
+    t = torch()
+    pl, of = _jpeg_payload(payload, offsets)
+    N = int(of.numel()) - 1
+    desc = t.empty((N, JPEG_DESC_WORDS), dtype=t.int32, device=pl.device)
+    _chk(_L().hq_jpeg_probe(ptr(pl) if pl.numel() else ptr(of), ptr(of), N, ptr(desc), stream()), exc)
+    return desc
+
+
+def jpeg_decode(payload, offsets, desc, ids, H: int, W: int, want_coefs: bool = False, exc=None):
+    """Decode payloads `ids` (a sequence of payload numbers; None = all) at frame size H x W -> (frames u8
+    [M, H, W], status int32 [M][, coefs int16 [M, blocks, 64] in zigzag order]) (hq_jpeg_decode).  status 0: the
+    frame holds libjpeg's (PIL's) pixels; otherwise it is zero and the payload is the host decoder's."""
+    t = torch()
+    pl, of = _jpeg_payload(payload, offsets)
+    N = int(of.numel()) - 1
+    if desc.dtype != t.int32 or tuple(desc.shape) != (N, JPEG_DESC_WORDS):
+        raise ValueError(f"desc must be jpeg_probe's int32 [{N}, {JPEG_DESC_WORDS}]")
+    if ids is None:
+        M, ids_t = N, None
+    else:
+        ids_h = np.asarray(ids, dtype=np.int64).reshape(-1)
+        if ids_h.size and (ids_h.min() < 0 or ids_h.max() >= N):
+            raise ValueError(f"ids must lie in [0, {N})")
+        M, ids_t = int(ids_h.size), t.from_numpy(ids_h).to(pl.device)
+    frames = t.empty((M, int(H), int(W)), dtype=t.uint8, device=pl.device)
+    status = t.empty(M, dtype=t.int32, device=pl.device)
+    coefs = t.empty((M, jpeg_blocks(int(H), int(W)), 64), dtype=t.int16, device=pl.device) if want_coefs else None
+    _chk(_L().hq_jpeg_decode(ptr(pl) if pl.numel() else ptr(of), ptr(of), ptr(_contig(desc)),
+                             ptr(ids_t) if ids_t is not None else None, M, int(H), int(W), ptr(frames), ptr(status),
+                             ptr(coefs) if coefs is not None else None, stream()), exc)
+    return (frames, status, coefs) if want_coefs else (frames, status)

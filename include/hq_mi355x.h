@@ -59,7 +59,8 @@ const char* hq_last_error(void);
  * "rank_win" (0: the long-list ranking by the bitonic sort alone, no window ranking), "rank_sort_nt" (512: lists
  * > 512 in 512-thread workgroups), "rank_sort_small" (0: lists <= 128 in the 1024-entry workgroup), "decode_nt"
  * (0: plain instead of non-temporal stores in hq_dequantize_unmap), "decode_generic" (1: its generic kernel
- * for every n), "cos_topk_hint" (0: hq_cos_topk without the running threshold between tiles).  Options are
+ * for every n), "cos_topk_hint" (0: hq_cos_topk without the running threshold between tiles), "jpeg_decode_f"
+ * (8, 32 or 64 instead of 16 frames per wave in hq_jpeg_decode).  Options are
  * process-wide: set them before launching, not
  * while other host threads launch.  hq_reset_option restores the default; hq_get_option returns 1 when
  * the option is set (value in *value), 0 when it is at its default, HQ_E_INVALID for an unknown name.
@@ -931,6 +932,37 @@ int hq_order_insert(const double* S, int64_t ldS, int Q, int64_t N, int64_t* pos
  *   non-NULL out is HQ_E_INVALID.                                                                             */
 int hq_jpeg_encode(const uint8_t* frames, int64_t N, int H, int W, int q, const int64_t* offsets, int32_t* lengths,
                    uint8_t* out, int16_t* coefs, hq_stream_t stream);
+
+/* ---- batched grayscale baseline JPEG decoder (csrc/hq_jpeg_decode.hip) -----------------------------
+ * The device form of the reconstruct path's JPEG stage (core/pipeline.py:183-235 of the reference: PIL on the host).
+ * Accepted payloads decode to the bytes libjpeg's default decoder (ISLOW integer inverse DCT; PIL) gives; every
+ * other payload gets a non-zero status and is left to the caller's host decoder.
+ * payload: the payloads back to back; offsets [N + 1] int64: payload i is payload[offsets[i] .. offsets[i + 1]).
+ * hq_jpeg_probe: one thread per payload walks the marker segments and writes desc [N, 8] int32: status, H, W, the
+ *   offsets (from the payload's first byte) of the 64 DQT entries, of the counts of the DC and of the AC Huffman
+ *   table the scan selects and of the first scan byte, one word unused.  Status 0 only for: SOI; APPn / COM
+ *   segments; 8-bit DQT; one SOF0 with precision 8 and one component sampled 1 x 1; DHT segments of one or several
+ *   tables that libjpeg accepts; DRI absent or 0; one SOS with that component, Ss = 0, Se = 63, Ah = Al = 0.  The
+ *   other values: 1 shorter than 4 bytes, 2 no SOI, 3 a segment that is malformed or runs past the payload, 4 another
+ *   SOFn (extended, progressive, ...), 5 SOF0 with other parameters (e.g. 3 components), 6 DQT (16-bit entries),
+ *   7 DHT (counts overflow the code space, more than 256 symbols, a DC symbol above 15), 8 a restart interval,
+ *   9 SOS with other parameters, 10 a table or the SOF missing at the SOS, 11 no SOS, 12 a marker it does not take,
+ *   18 offsets that do not bound a payload (or longer than 2^30 bytes).
+ * hq_jpeg_decode: frames [M, H, W] u8 and status [M] int32 for payloads ids[0 .. M) (int64; NULL: payloads 0 .. M-1;
+ *   every id must be a payload of offsets / desc, a negative one is status 18).  Status 0 = decoded; otherwise the
+ *   descriptor's status, or 13 the scan needs bits past the payload's end or past a marker, 14 corrupt (a code
+ *   longer than 16 bits, a coefficient index past 63, a size above 11 (DC) or 10 (AC)), 15 no FF D9 right after the
+ *   scan, 16 the payload's H, W are not the call's, 17 a dequantised coefficient or a first-pass value beyond
+ *   +-16383 or a pixel beyond [-512, 511] before the clamp (where libjpeg's C and SIMD forms part ways): the
+ *   frame's H x W bytes are then zero.  The kernel ends after blocks x 64 symbols whatever the bytes are, reads
+ *   payload i only inside its offsets and writes frame j only inside its H x W bytes.
+ * coefs, when non-NULL: [M, blocks, 64] int16, the decoded coefficients in zigzag order (hq_jpeg_encode's layout).
+ * Limits: grayscale baseline without restart intervals, W <= 224 and H <= 65500 (else HQ_E_UNSUPPORTED).
+ * N == 0 or M == 0 returns HQ_OK without a launch; a NULL payload, offsets, desc, frames or status, a negative
+ *   count and H, W < 1 are HQ_E_INVALID.  All argument checks return before any device work.                  */
+int hq_jpeg_probe(const uint8_t* payload, const int64_t* offsets, int64_t N, int32_t* desc, hq_stream_t stream);
+int hq_jpeg_decode(const uint8_t* payload, const int64_t* offsets, const int32_t* desc, const int64_t* ids, int64_t M,
+                   int H, int W, uint8_t* frames, int32_t* status, int16_t* coefs, hq_stream_t stream);
 
 /* ---- §8e: the sharded search's one collective (RCCL over xGMI) ----------------------------------
  * The corpus is split into contiguous global-id ranges, one per GPU (one process per GPU); each rank
