@@ -159,6 +159,10 @@ SIGNATURES = {
     "hq_jpeg_encode": (_i, [_p, _i64, _i, _i, _i, _p, _p, _p, _p, _p]),
     "hq_jpeg_probe": (_i, [_p, _p, _i64, _p, _p]),
     "hq_jpeg_decode": (_i, [_p, _p, _p, _p, _i64, _i, _i, _p, _p, _p, _p]),
+    "hq_ssim_maps_bytes": (_sz, [_i, _i]),
+    "hq_ssim_prepare": (_i, [_p, _i64, _i, _i, _p, _p, _p]),
+    "hq_ssim_scores": (_i, [_p, _p, _p, _i, _p, _i64, _i, _i, _p, _p, _p]),
+    "hq_ssim_scores_listed": (_i, [_p, _p, _p, _i, _p, _i64, _i, _i, _p, _i, _p, _p, _p]),
 }
 
 _lock = threading.Lock()

@@ -1780,3 +1780,81 @@ def jpeg_decode(payload, offsets, desc, ids, H: int, W: int, want_coefs: bool = 
                              ptr(ids_t) if ids_t is not None else None, M, int(H), int(W), ptr(frames), ptr(status),
                              ptr(coefs) if coefs is not None else None, stream()), exc)
     return (frames, status, coefs) if want_coefs else (frames, status)
+
+
+# ------------------------------------------------ Gaussian-window SSIM of u8 frame pairs (hq_ssim.hip)
+
+SSIM_MIN_SIDE, SSIM_MAX_H, SSIM_MAX_W = 4, 131, 128
+
+
+class SsimFrames:
+    """u8 frames [N, H, W] with their prepared maps (float64 [N, 2, H, W]: mean and variance of the normalised
+    frame under the 7 x 7 Gaussian) and stats (float64 [N, 4]: min, max, sum, sum of squares)."""
+    __slots__ = ("frames", "maps", "stats")
+
+    def __init__(self, frames, maps, stats):
+        self.frames, self.maps, self.stats = frames, maps, stats
+
+
+def _ssim_frames(frames_u8):
+    t = torch()
+    if frames_u8.dtype != t.uint8:
+        raise TypeError(f"SSIM takes uint8 frames, got {frames_u8.dtype}")
+    fr = frames_u8.unsqueeze(0) if frames_u8.dim() == 2 else frames_u8
+    if fr.dim() != 3:
+        raise ValueError("frames must be [N, H, W] (or one [H, W] frame)")
+    return _contig(fr)
+
+
+def ssim_prepare(frames_u8, exc=None) -> SsimFrames:
+    """u8 frames [N, H, W] -> SsimFrames (hq_ssim_prepare, one launch): the query side of ssim_scores."""
+    t = torch()
+    fr = _ssim_frames(frames_u8)
+    N, H, W = (int(d) for d in fr.shape)
+    maps = t.empty((N, 2, H, W), dtype=t.float64, device=fr.device)
+    stats = t.empty((N, 4), dtype=t.float64, device=fr.device)
+    _chk(_L().hq_ssim_prepare(ptr(fr), N, H, W, ptr(maps), ptr(stats), stream()), exc)
+    if N and int(_L().hq_ssim_maps_bytes(H, W)) != 16 * H * W:
+        raise RuntimeError("hq_ssim_maps_bytes disagrees with the maps layout")
+    return SsimFrames(fr, maps, stats)
+
+
+def _ssim_pair(q: SsimFrames, frames_u8):
+    c = _ssim_frames(frames_u8)
+    if tuple(c.shape[1:]) != tuple(q.frames.shape[1:]):
+        raise ValueError(f"frames differ: {tuple(q.frames.shape[1:])} vs {tuple(c.shape[1:])}")
+    return c
+
+
+def ssim_scores(q: SsimFrames, frames_u8, ncc: bool = False, exc=None):
+    """SSIM of every prepared query against every raw u8 frame [N, H, W] -> device f64 [Q, N] (hq_ssim_scores, one
+    launch); ncc=True adds the template correlation (Pearson of the raw pixels, 0.0 for a constant frame) [Q, N]."""
+    t = torch()
+    c = _ssim_pair(q, frames_u8)
+    Q, H, W = (int(d) for d in q.frames.shape)
+    N = int(c.shape[0])
+    out = t.empty((Q, N), dtype=t.float64, device=c.device)
+    on = t.empty((Q, N), dtype=t.float64, device=c.device) if ncc else None
+    _chk(_L().hq_ssim_scores(ptr(q.frames), ptr(q.maps), ptr(q.stats), Q, ptr(c), N, H, W, ptr(out), ptr(on),
+                             stream()), exc)
+    return (out, on) if ncc else out
+
+
+def ssim_scores_listed(q: SsimFrames, frames_u8, ids, ncc: bool = False, exc=None):
+    """ssim_scores through an id list (hq_ssim_scores_listed, one launch): ids int64 [Q, C] -> device f64 [Q, C], entry
+    (a, j) bit for bit what ssim_scores writes for (query a, frame ids[a, j]); the frames are read in place.  An id
+    < 0 or >= N is a pad: -inf in both outputs."""
+    t = torch()
+    c = _ssim_pair(q, frames_u8)
+    Q, H, W = (int(d) for d in q.frames.shape)
+    N = int(c.shape[0])
+    il = _contig(ids.to(t.int64))
+    if il.dim() != 2 or int(il.shape[0]) != Q:
+        raise ValueError(f"ids {tuple(il.shape)} for {Q} queries")
+    C = int(il.shape[1])
+    out = t.empty((Q, C), dtype=t.float64, device=c.device)
+    on = t.empty((Q, C), dtype=t.float64, device=c.device) if ncc else None
+    if C:
+        _chk(_L().hq_ssim_scores_listed(ptr(q.frames), ptr(q.maps), ptr(q.stats), Q, ptr(c) if N else None, N, H, W,
+                                        ptr(il), C, ptr(out), ptr(on), stream()), exc)
+    return (out, on) if ncc else out

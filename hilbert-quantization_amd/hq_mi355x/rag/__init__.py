@@ -5,10 +5,12 @@ float32 queries at full precision (search_float, search_parameters(quantize_quer
 ComprehensiveFrameCorpus ranks enhanced frames by the engine's comprehensive similarity (hierarchical + embedding +
 spatial), fused into one matrix-core contraction for a store written by one generator.
 HierarchicalFrameCorpus runs the engine's progressive hierarchical search (the candidate cascade over the index rows
-that precedes that ranking) for whole query batches on the device."""
+that precedes that ranking) for whole query batches on the device.
+FrameSSIMCorpus keeps u8 frames resident for the Gaussian-window SSIM: dense scores, top-k and the listed re-score of
+the hybrid search's second stage."""
 from .hilbert_mapper import HilbertCurveMapperImpl
 from .hierarchical_index_generator import HierarchicalIndexGenerator
-from .similarity import (ComprehensiveFrameCorpus, FrameCosineCorpus, HierarchicalFrameCorpus, QuantizedFrameCorpus,
+from .similarity import (ComprehensiveFrameCorpus, FrameCosineCorpus, FrameSSIMCorpus, HierarchicalFrameCorpus, QuantizedFrameCorpus,
                          apply_progressive_threshold, progressive_hierarchical_search,
                          calculate_comprehensive_similarity, calculate_embedding_similarity, comprehensive_scores,
                          comprehensive_scores_listed,
@@ -18,7 +20,7 @@ from .similarity import (ComprehensiveFrameCorpus, FrameCosineCorpus, Hierarchic
                          cosine_topk_batch, detect_original_embedding_height, extract_original_embedding,
                          progressive_threshold, progressive_threshold_batch, spatial_locality_scores)
 
-__all__ = ["ComprehensiveFrameCorpus", "HierarchicalFrameCorpus", "progressive_hierarchical_search", "calculate_comprehensive_similarity", "calculate_embedding_similarity",
+__all__ = ["ComprehensiveFrameCorpus", "FrameSSIMCorpus", "HierarchicalFrameCorpus", "progressive_hierarchical_search", "calculate_comprehensive_similarity", "calculate_embedding_similarity",
            "comprehensive_scores", "comprehensive_scores_listed", "similarity_weights", "FrameCosineCorpus", "HilbertCurveMapperImpl", "HierarchicalIndexGenerator", "QuantizedFrameCorpus",
            "apply_progressive_threshold",
            "calculate_embedding_cosine_similarity", "calculate_granularity_weights",

@@ -87,6 +87,42 @@ class FrameCosineCorpus:
         return K.cosine_topk(K.cos_prepare(q2), self._rows, int(k), thr, mode)
 
 
+class FrameSSIMCorpus:
+    """u8 frames [N, H, W] (4 x 4 to 131 x 128) kept resident as they are, 1 byte per pixel, for the reference's
+    Gaussian-window SSIM (core/cv_features.py calculate_ssim): queries are prepared per call (their filtered maps,
+    16 bytes per pixel), the corpus is streamed raw.  rescore() is the second stage of the reference's hybrid
+    search (_hybrid_search_optimized: image features on the hierarchical stage's top 2 max_results)."""
+
+    def __init__(self, frames_u8):
+        self._frames = K._ssim_frames(to_dev(frames_u8))
+        self.shape = tuple(int(d) for d in self._frames.shape[1:])
+        K.ssim_prepare(self._frames[:0])  # refuses a frame shape outside the kernel's limits now, not at search time
+
+    @property
+    def N(self) -> int:
+        return int(self._frames.shape[0])
+
+    def __len__(self) -> int:
+        return self.N
+
+    def scores(self, queries, ncc: bool = False):
+        """queries u8 [Q, H, W] (or one frame) -> device float64 [Q, N] (with ncc=True: (ssim, template
+        correlation))."""
+        return K.ssim_scores(K.ssim_prepare(to_dev(queries)), self._frames, ncc=ncc)
+
+    def rescore(self, queries, ids, ncc: bool = False):
+        """The scores of the listed frames only: ids int64 [Q, C] -> device float64 [Q, C], bit for bit the entries
+        of scores(); an id < 0 or >= N is a pad and scores -inf."""
+        return K.ssim_scores_listed(K.ssim_prepare(to_dev(queries)), self._frames, to_dev(ids), ncc=ncc)
+
+    def search(self, queries, k: int = 10, threshold=None):
+        """-> device (scores [Q, k] f64, ids [Q, k] i64) by (score desc, frame asc), -inf / -1 where fewer than k
+        frames pass `threshold` (None: no test; else score >= threshold): select_topk over the dense scores."""
+        thr, mode = _threshold_mode(threshold)
+        s, ids, _, _ = K.select_topk(self.scores(queries), int(k), thr, mode)
+        return s, ids
+
+
 class QuantizedFrameCorpus(ResidentRows):
     """The store's own u8 frames [N, r, c] with their (min, max) pairs [N, 2], prepared once for the exact
     integer cosine (hq_cosq_prepare) and searched without decoding: only the signed bytes (1 B per value, in

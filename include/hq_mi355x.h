@@ -964,6 +964,39 @@ int hq_jpeg_probe(const uint8_t* payload, const int64_t* offsets, int64_t N, int
 int hq_jpeg_decode(const uint8_t* payload, const int64_t* offsets, const int32_t* desc, const int64_t* ids, int64_t M,
                    int H, int W, uint8_t* frames, int32_t* status, int16_t* coefs, hq_stream_t stream);
 
+/* ---- Gaussian-window SSIM and template correlation of u8 frame pairs (csrc/hq_ssim.hip) -------------
+ * The device form of core/cv_features.py:386-457 (calculate_ssim) with :657-704 (_calculate_ssim_manual), for two u8
+ * frames x, y [H, W]: each normalised in float64, x' = (x - min x) / (max x - min x + 1e-8) (a constant frame is all
+ * zeros); g = the 7 taps exp(-(i - 3)^2 / 4.5) normalised to sum 1 (cv2.getGaussianKernel(7, 1.5)); F = the
+ * separable 7 x 7 correlation with g (x) g, borders mirrored without repeating the edge pixel (BORDER_REFLECT_101);
+ * mu1 = F(x'), mu2 = F(y'), var1 = F(x'^2) - mu1^2, var2 likewise, cov = F(x'y') - mu1 mu2, C1 = 1e-4, C2 = 9e-4;
+ *   ssim = mean over the H W pixels of (2 mu1 mu2 + C1)(2 cov + C2) / ((mu1^2 + mu2^2 + C1)(var1 + var2 + C2) + 1e-8).
+ * Float64 from the integer products on: within 1e-5 of a float64 model of those lines on every frame family tested
+ * (profiles/ssim_error_bounds.txt has the measured error).  win_size 7 is the only window.
+ * ncc = the Pearson correlation of the raw pixels (cv2.matchTemplate TM_CCOEFF_NORMED of equal-sized frames), in
+ *   float64 from exact integer sums; 0.0 when either frame is constant.
+ * Frames: 4 <= H <= 131 and 4 <= W <= 128 (one reflection reaches every border pixel; a strip of the frame, its
+ *   filter tile and two query strips fit 64 KiB of LDS); anything else is HQ_E_UNSUPPORTED before any launch.
+ * hq_ssim_maps_bytes: bytes of one frame's prepared maps, 16 H W (0 for a frame outside the limits).
+ * hq_ssim_prepare: frames [N, H, W] u8 -> maps [N, 2, H, W] float64 (mu and var of the normalised frame) and stats
+ *   [N, 4] float64 = (min, max, sum x, sum x^2).  One launch.
+ * hq_ssim_scores: queries q [Q, H, W] u8 with their prepared maps and stats against raw frames c [N, H, W] u8 ->
+ *   out_ssim [Q, N] float64 and, when out_ncc is not NULL, out_ncc [Q, N].  A workgroup owns one corpus frame: it
+ *   filters that frame's maps once and walks a tile of at most 32 queries.  One launch.
+ * hq_ssim_scores_listed: ids int64 [Q, C] -> out [Q, C]: entry (a, j) is the value hq_ssim_scores writes for the pair
+ *   (query a, frame ids[a, j]), bit for bit (both kernels call one per-pair device function).  ids[a, j] < 0 or >= N
+ *   is a pad: -inf in both outputs, no frame is read (c may be NULL when N = 0).  Repeated ids are allowed.  1 <= C
+ *   <= 65535, anything else is HQ_E_INVALID.  One launch.
+ * Q = 0 or N = 0 (dense, prepare) returns HQ_OK without a launch.  NULL buffers and maps, stats, ids or outputs that
+ *   are not 8-byte aligned are HQ_E_INVALID.  All argument checks return before any device work.                */
+size_t hq_ssim_maps_bytes(int H, int W);
+int hq_ssim_prepare(const uint8_t* frames, int64_t N, int H, int W, void* maps, double* stats, hq_stream_t stream);
+int hq_ssim_scores(const uint8_t* q, const void* q_maps, const double* q_stats, int Q, const uint8_t* c, int64_t N,
+                   int H, int W, double* out_ssim, double* out_ncc, hq_stream_t stream);
+int hq_ssim_scores_listed(const uint8_t* q, const void* q_maps, const double* q_stats, int Q, const uint8_t* c,
+                          int64_t N, int H, int W, const int64_t* ids, int C, double* out_ssim, double* out_ncc,
+                          hq_stream_t stream);
+
 /* ---- §8e: the sharded search's one collective (RCCL over xGMI) ----------------------------------
  * The corpus is split into contiguous global-id ranges, one per GPU (one process per GPU); each rank
  * answers the whole query batch against its shard and packs fixed-size top-k records, and ONE
