@@ -163,6 +163,9 @@ SIGNATURES = {
     "hq_ssim_prepare": (_i, [_p, _i64, _i, _i, _p, _p, _p]),
     "hq_ssim_scores": (_i, [_p, _p, _p, _i, _p, _i64, _i, _i, _p, _p, _p]),
     "hq_ssim_scores_listed": (_i, [_p, _p, _p, _i, _p, _i64, _i, _i, _p, _i, _p, _p, _p]),
+    "hq_vfeat_extract": (_i, [_p, _i64, _i, _i, _p, _p]),
+    "hq_vfeat_scores": (_i, [_p, _i, _p, _i64, _p, _p, _p]),
+    "hq_vfeat_scores_listed": (_i, [_p, _i, _p, _i64, _p, _p, _i, _p, _p, _p, _p]),
 }
 
 _lock = threading.Lock()

@@ -11,10 +11,12 @@ from .precomputed_hilbert_index import (PrecomputedHilbertIndexer, PrecomputedSi
 from .frame_order import (FrameOrdering, sort_frames_by_hierarchical_indices, frame_ordering_metrics,
                           find_optimal_insertion_position)
 from .cv_features import calculate_ssim, ssim_scores, ssim_scores_listed, template_correlation
+from .video_search import VideoFeatureIndex, extract_video_features
 
 __all__ = ["PowerOf4DimensionCalculator", "HilbertCurveMapper", "StreamingHilbertIndexGenerator",
            "HierarchicalIndexGeneratorImpl", "MPEGAICompressorImpl", "ProgressiveSimilaritySearchEngine",
            "LevelConfig", "IndexCorpus", "QuantizationPipeline", "quantize_batch", "PrecomputedHilbertIndexer",
            "PrecomputedSimilaritySearchEngine", "PrecomputedIndex", "PrecomputedLevel", "FrameOrdering",
            "sort_frames_by_hierarchical_indices", "frame_ordering_metrics", "find_optimal_insertion_position",
-           "calculate_ssim", "ssim_scores", "ssim_scores_listed", "template_correlation"]
+           "calculate_ssim", "ssim_scores", "ssim_scores_listed", "template_correlation",
+           "VideoFeatureIndex", "extract_video_features"]

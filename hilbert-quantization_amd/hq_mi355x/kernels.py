@@ -1858,3 +1858,85 @@ def ssim_scores_listed(q: SsimFrames, frames_u8, ids, ncc: bool = False, exc=Non
         _chk(_L().hq_ssim_scores_listed(ptr(q.frames), ptr(q.maps), ptr(q.stats), Q, ptr(c) if N else None, N, H, W,
                                         ptr(il), C, ptr(out), ptr(on), stream()), exc)
     return (out, on) if ncc else out
+
+
+# ------------------------------------------------ video features of u8 frames and their scorer (hq_vfeat.hip)
+
+VFEAT_MIN_SIDE, VFEAT_MAX_PIXELS = 4, 131 * 128
+VFEAT_WEIGHTS = (0.3, 0.2, 0.1)  # histogram, texture, stats (core/video_search.py:1503; the ORB part is not computed)
+
+
+class VfeatRows:
+    """Feature rows f64 [N, 64] of hq_vfeat_extract: [0, 32) histogram, [32, 48) texture, [48, 55) stats, [55] 0,
+    [56, 59) the three part norms, [59, 64) 0."""
+    __slots__ = ("rows",)
+
+    def __init__(self, rows):
+        self.rows = rows
+
+    def __len__(self) -> int:
+        return int(self.rows.shape[0])
+
+    def features(self):
+        """The [N, 55] feature values (a view)."""
+        return self.rows[:, :55]
+
+
+def _vfeat_weights(weights):
+    w = VFEAT_WEIGHTS if weights is None else tuple(float(v) for v in weights)
+    if len(w) != 3:
+        raise ValueError(f"weights are (histogram, texture, stats), got {len(w)} values")
+    return (ctypes.c_double * 3)(*w)
+
+
+def vfeat_extract(frames_u8, exc=None) -> VfeatRows:
+    """u8 frames [N, H, W] (or one [H, W] frame) -> VfeatRows (hq_vfeat_extract, one launch, one wave per frame)."""
+    t = torch()
+    if frames_u8.dtype != t.uint8:
+        raise TypeError(f"video features take uint8 frames, got {frames_u8.dtype}")
+    fr = frames_u8.unsqueeze(0) if frames_u8.dim() == 2 else frames_u8
+    if fr.dim() != 3:
+        raise ValueError("frames must be [N, H, W] (or one [H, W] frame)")
+    fr = _contig(fr)
+    N, H, W = (int(d) for d in fr.shape)
+    if min(H, W) < VFEAT_MIN_SIDE or H * W > VFEAT_MAX_PIXELS:
+        raise ValueError(f"video-feature frames have sides >= {VFEAT_MIN_SIDE} and at most {VFEAT_MAX_PIXELS} "
+                         f"pixels, got {H} x {W}")
+    rows = t.empty((N, 64), dtype=t.float64, device=fr.device)
+    _chk(_L().hq_vfeat_extract(ptr(fr), N, H, W, ptr(rows), stream()), exc)
+    return VfeatRows(rows)
+
+
+def vfeat_scores(q: VfeatRows, c: VfeatRows, weights=None, exc=None):
+    """Every query row against every corpus row -> device f64 [Q, N] (hq_vfeat_scores, one launch): the weighted sum
+    of the three parts' clamped cosines; weights default to VFEAT_WEIGHTS."""
+    t = torch()
+    Q, N = len(q), len(c)
+    out = t.empty((Q, N), dtype=t.float64, device=c.rows.device)
+    _chk(_L().hq_vfeat_scores(ptr(q.rows), Q, ptr(c.rows), N, _vfeat_weights(weights), ptr(out), stream()), exc)
+    return out
+
+
+def vfeat_scores_listed(q: VfeatRows, c: VfeatRows, ids, hier=None, weights=None, exc=None):
+    """vfeat_scores through an id list (hq_vfeat_scores_listed, one launch): ids int64 [Q, C] -> video f64 [Q, C],
+    entry (a, j) bit for bit what vfeat_scores writes for (query a, row ids[a, j]); an id < 0 or >= N is a pad: -inf.
+    With hier f64 [Q, C] (the hierarchical scores of the same entries) returns (video, combined), combined = v > 0.5 ?
+    0.3 h + 0.7 v : 0.8 h + 0.2 v."""
+    t = torch()
+    Q, N = len(q), len(c)
+    il = _contig(ids.to(t.int64))
+    if il.dim() != 2 or int(il.shape[0]) != Q:
+        raise ValueError(f"ids {tuple(il.shape)} for {Q} queries")
+    C = int(il.shape[1])
+    hr = None
+    if hier is not None:
+        hr = _contig(hier.to(t.float64))
+        if hr.shape != il.shape:
+            raise ValueError(f"hier {tuple(hr.shape)} and ids {tuple(il.shape)}")
+    video = t.empty((Q, C), dtype=t.float64, device=c.rows.device)
+    comb = t.empty((Q, C), dtype=t.float64, device=c.rows.device) if hr is not None else None
+    if C:
+        _chk(_L().hq_vfeat_scores_listed(ptr(q.rows), Q, ptr(c.rows) if N else None, N, _vfeat_weights(weights),
+                                         ptr(il), C, ptr(hr) if hr is not None else None, ptr(video),
+                                         ptr(comb) if comb is not None else None, stream()), exc)
+    return (video, comb) if hr is not None else video

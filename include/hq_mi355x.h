@@ -997,6 +997,40 @@ int hq_ssim_scores_listed(const uint8_t* q, const void* q_maps, const double* q_
                           int64_t N, int H, int W, const int64_t* ids, int C, double* out_ssim, double* out_ncc,
                           hq_stream_t stream);
 
+/* ---- Video-feature search: per-frame feature rows and their weighted clamped-cosine scorer (csrc/hq_vfeat.hip) ----
+ * The device form of core/video_search.py's `video_features` and `hybrid` searches (_extract_comprehensive_features
+ * :1347, _extract_texture_features :1390, _calculate_feature_similarity :1499, _hybrid_search_optimized :1576) for
+ * gray u8 frames g [H, W], n = H W.  A feature row is 64 float64 values (512 bytes):
+ *   [0, 32)  histogram: the count of g >> 3 (cv2.calcHist, 32 bins over [0, 256)), exact.
+ *   [32, 48) texture, from the 3 x 3 Sobel derivatives gx = (p[-1,+1] + 2 p[0,+1] + p[+1,+1]) - (p[-1,-1] + 2 p[0,-1] +
+ *            p[+1,-1]) and gy (its transpose), borders mirrored without the edge pixel (p[-1] = p[1]), m = sqrt(gx^2 +
+ *            gy^2): mean m, std m, mean gx, std gx, mean gy, std gy, mean |gx|, mean |gy| (population std), then the
+ *            8 counts of np.histogram(m, bins=8): with lo, hi = min m, max m (lo - 0.5, hi + 0.5 when equal) and
+ *            edge_j = j ((hi - lo) / 8) + lo in float64 without contraction, bin(x) = #{j in 1 .. 7 : x >= edge_j}.
+ *            The counts are exact; means and variances of gx, gy come from exact integer sums.
+ *   [48, 55) stats: mean, std, min, max, median, 25th and 75th percentile of g (NumPy's linear interpolation at
+ *            q (n - 1)), all from the exact 256-bin histogram.
+ *   [55]     0 (pads the stats part to 8 values);  [56, 59) the Euclidean norms of the three parts;  [59, 64) 0.
+ * A pair of rows scores  ((w[0] c_h) + w[1] c_t) + w[2] c_s  with  c = (|a| > 0 and |b| > 0) ? max(0, a.b / (|a| |b|))
+ * : 0  per part, in float64; the reference's weights are 0.3, 0.2, 0.1.  Its fourth part (ORB descriptors, weight
+ * 0.4) is not computed: see DESIGN.md §7.
+ * hq_vfeat_extract: frames [N, H, W] u8 -> rows [N, 64].  One wave per frame, one launch.  Frames: H, W >= 4 and
+ *   H W <= 16768 (131 x 128); anything else is HQ_E_UNSUPPORTED before any launch.
+ * hq_vfeat_scores: qrows [Q, 64] x crows [N, 64] -> out [Q, N] float64.  w: three HOST doubles, finite and >= 0.
+ * hq_vfeat_scores_listed: ids int64 [Q, C] -> video [Q, C]: entry (a, j) is the value hq_vfeat_scores writes for
+ *   (query a, row ids[a, j]), bit for bit (one fma chain per part in both kernels, one device function for the
+ *   rest).  ids[a, j] < 0 or >= N is a pad: -inf in both outputs, no row is read (crows may be NULL when N = 0).
+ *   hier [Q, C] and combined [Q, C] are given together or both NULL: combined = v > 0.5 ? 0.3 h + 0.7 v : 0.8 h + 0.2 v
+ *   (the hybrid search's blend of the hierarchical score h with the video score v).  1 <= C <= 65535.
+ * Q = 0 or N = 0 (dense, extract) returns HQ_OK without a launch.  NULL buffers, and rows, ids or outputs that are
+ *   not 8-byte aligned, are HQ_E_INVALID.  All argument checks return before any device work.                  */
+int hq_vfeat_extract(const uint8_t* frames, int64_t N, int H, int W, double* rows, hq_stream_t stream);
+int hq_vfeat_scores(const double* qrows, int Q, const double* crows, int64_t N, const double* w, double* out,
+                    hq_stream_t stream);
+int hq_vfeat_scores_listed(const double* qrows, int Q, const double* crows, int64_t N, const double* w,
+                           const int64_t* ids, int C, const double* hier, double* video, double* combined,
+                           hq_stream_t stream);
+
 /* ---- §8e: the sharded search's one collective (RCCL over xGMI) ----------------------------------
  * The corpus is split into contiguous global-id ranges, one per GPU (one process per GPU); each rank
  * answers the whole query batch against its shard and packs fixed-size top-k records, and ONE
