@@ -46,7 +46,6 @@ enum Opt {
   OPT_CHUNK_NT, OPT_CHUNK_EXACTDIV, OPT_CHUNK_GENERIC, OPT_CHUNK_WPB, OPT_CHUNK_CPW,
   OPT_PRECOMP_NT, OPT_PRECOMP_TREE_LDS, OPT_PRECOMP_PAD, OPT_PRECOMP_SKIP, OPT_PRECOMP_GRID, OPT_PRECOMP_PF,
   OPT_PRECOMP_DIAG,
-  OPT_COS_KERNEL,
   OPT_SAMPLE_KTH,
   OPT_SCAN_V1,
   OPT_REFINE_GLOBAL, OPT_SELECT_2STAGE, OPT_LEVEL_SCORES_V1,

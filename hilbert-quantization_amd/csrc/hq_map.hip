@@ -36,7 +36,6 @@ static const char* const kOptNames[OPT_COUNT] = {
     "chunk_nt", "chunk_exactdiv", "chunk_generic", "chunk_wpb", "chunk_cpw",
     "precomp_nt", "precomp_tree_lds", "precomp_pad", "precomp_skip", "precomp_grid", "precomp_pf",
     "precomp_diag",
-    "cos_kernel",
     "sample_kth",
     "scan_v1",
     "refine_global", "select_2stage", "level_scores_v1",
@@ -68,10 +67,7 @@ __attribute__((constructor)) static void opt_from_env() {
     }
     const char* v = getenv(env);
     if (!v) continue;
-    int64_t x = atoll(v);
-    if (i == OPT_COS_KERNEL) x = strcmp(v, "regstage") == 0 ? 1 : strcmp(v, "lockstep") == 0 ? 2
-                                 : strcmp(v, "temporal") == 0 ? 3 : x;
-    g_opt_val[i] = x;
+    g_opt_val[i] = atoll(v);
     g_opt_set[i] = true;
   }
 }

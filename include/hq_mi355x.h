@@ -52,8 +52,8 @@ const char* hq_last_error(void);
  * Every entry point runs its tuned kernel by default and a default build never reads the environment.
  * hq_set_option selects an alternative form of a kernel (same results, checked by the parity tests):
  * e.g. "fused_v" (fused-kernel variant bits), "fused_generic", "chunk_generic", "chunk_exactdiv",
- * "chunk_wpb", "chunk_cpw", "precomp_grid", "precomp_tree_lds", "cos_kernel" (1 register-staged,
- * 2 lockstep), "refine_global", "select_2stage", "level_scores_v1" (the one-thread-per-pair dense scorer),
+ * "chunk_wpb", "chunk_cpw", "precomp_grid", "precomp_tree_lds",
+ * "refine_global", "select_2stage", "level_scores_v1" (the one-thread-per-pair dense scorer),
  * "sample_kth" (0 = provable bound), "scan_v1" (the LDS-tiled f64 scans instead of the split-f16 ones),
  * "rank_ct" (0: the long-list re-rank's runtime level structure; 2: the compile-time one in the short-list kernel too),
  * "rank_win" (0: the long-list ranking by the bitonic sort alone, no window ranking), "rank_sort_nt" (512: lists
@@ -562,9 +562,9 @@ int hq_precomputed_similarity(const float* q_avgs, const float* q_norm, const fl
  * hq_cos_prepare: f32 rows X [N, K] (row stride ld) -> split-f16 copies X16 of hq_cos_padded_rows(N) x 2 x
  *   hq_cos_padded_k(K) halves (power-of-two scaled hi / lo halves in 1 KiB MFMA operand fragments: 16-row
  *   tile t, K step kb of 32, plane p at ((t KB + kb) 2 + p) x 512 halves, lane 16 g + j = row 16 t + j,
- *   k = 32 kb + 8 g .. + 7; the superseded kernels of option cos_kernel 1-3 use rows [N, 2, Kp]) and
+ *   k = 32 kb + 8 g .. + 7) and
  *   inv [padded rows] = 1 / (scale |x|) (0 for a zero row).  Prepare a corpus once, each query batch per
- *   call, under the same cos_kernel option as the scoring call.
+ *   call.
  * hq_cos_scores_mfma: out [Q, N] f64 = (cos + 1) / 2 (0 when a norm is 0), split-f16 MFMA contraction
  *   (v_mfma_f32_16x16x32_f16 x 3), within 1e-5 of the exact cosine and of the reference's float32 BLAS result
  *   for K <= 16384.  The error depends on the rows (profiles/cos_error_bounds.txt, measured per row family):
@@ -588,7 +588,7 @@ int hq_cos_scores_mfma_f32(const void* A16, const double* inv_a, int Q, const vo
                            int K, float* out, hq_stream_t stream);
 
 /* hq_cos_topk: the nearest k frames of every query without the Q x N score matrix.  Operands as for
- *   hq_cos_scores_mfma in the default tiled layout (option cos_kernel 1-3: HQ_E_UNSUPPORTED).  out_score /
+ *   hq_cos_scores_mfma.  out_score /
  *   out_id [Q, k]: the best k frames among those passing thr_mode (0 none, 1 >= threshold, 2 > threshold), in
  *   (score descending, id ascending) order, ids = frame + id_base, empty slots -inf / -1.  The scores are the
  *   float64 values hq_cos_scores_mfma writes for those pairs, bit for bit, and the lists equal

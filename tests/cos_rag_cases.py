@@ -118,7 +118,7 @@ def spatial_exact(e1, e2):
 
 
 def model_prepare(X, scale="ldexp"):
-    """k_cos_prepare's arithmetic: amax (NaN ignored, as fmaxf), e = frexp exponent (0 for a zero row),
+    """k_cos_prepare_tiled's arithmetic: amax (NaN ignored, as fmaxf), e = frexp exponent (0 for a zero row),
     v = s x with s = 2^-e, hi = f16(v), lo = f16(v - hi), inv = 1 / (s |x|) from the f64 norm.
     scale "mul": x * ldexpf(1, -e) and 1 / (s sqrt(ss)), the expression before the fix (s overflows to inf for
     a subnormal amax); "ldexp": ldexpf(x, -e) and ldexp(1 / sqrt(ss), e).  -> hi, lo (float32 holding f16

@@ -57,11 +57,9 @@ def test_cos_topk_argument_validation(lib):
     assert need > 0
     assert call(wb=need - 1) == _lib.HQ_E_INVALID
     assert _lib.last_error() == "workspace too small"
-    # the row-major layout of the superseded kernels is refused with a message
-    for code in (1, 2, 3):
-        with _lib.option("cos_kernel", code):
-            assert call() == _lib.HQ_E_UNSUPPORTED
-            assert f"cos_kernel={code}" in _lib.last_error() and "tiled" in _lib.last_error()
+    # the option that selected the superseded row-major kernels is gone: setting it is an error, not a no-op
+    with pytest.raises(_lib.NativeLibraryError, match="unknown option 'cos_kernel'"):
+        _lib.set_option("cos_kernel", 1)
     assert _lib.get_option("cos_topk_hint") is None
     with _lib.option("cos_topk_hint", 0):
         assert _lib.get_option("cos_topk_hint") == 0

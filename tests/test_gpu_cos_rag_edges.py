@@ -92,20 +92,6 @@ def test_cosine_route_consistency(hq_lib, fam):
     assert np.max(np.abs(at[:, : N - 1] - below)) <= C.bound(fam, K)
 
 
-@pytest.mark.parametrize("K", (1000, 4096))
-@pytest.mark.parametrize("fam", ("subnormal", "huge"))
-def test_mfma_cosine_rowmajor_prepare(hq_lib, hq_option, fam, K):
-    """cos_kernel 1 (row-major k_cos_prepare + the register-staged kernel) on the rows whose scale leaves the
-    float32 range: the same bound, and the same bits as the default tiled route."""
-    from hq_mi355x import kernels as K_
-    A, B, exact, s64, _ = _mfma(fam, K)
-    hq_option("cos_kernel", 1)
-    got = _np(K_.cosine_scores_mfma(K_.cos_prepare(_dev(A)), K_.cos_prepare(_dev(B))))
-    hq_option("cos_kernel", None)
-    _check_family(fam, K, got, exact)
-    assert got.tobytes() == s64.tobytes()
-
-
 # ------------------------------------------------------- hq_cosine_scores / hq_cosine_scores_dt (f64 kernels)
 
 

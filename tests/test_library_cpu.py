@@ -170,7 +170,7 @@ def test_kernel_options_are_explicit(lib):
 REMOVED_OPTIONS = (
     "scan_variant", "scan_wpb", "scan_nb", "scan_pf", "scan_occ", "scan_split3", "scan_nosample", "scan_expt",
     "refine_expt", "sample_variant", "sample_hi", "sample_stride", "sample_waves", "ov_occ", "ov_pf", "ov_waves",
-    "scanov_split3", "scanov_v1", "seg_prepare_flat", "final_rounds")
+    "scanov_split3", "scanov_v1", "seg_prepare_flat", "final_rounds", "cos_kernel")
 KEPT_SEARCH_OPTIONS = (
     "sample_kth", "scan_v1", "refine_global", "refine_coop", "refine_small", "select_2stage", "level_scores_v1",
     "prep_coop", "pool_sort_mem", "rank_ct", "rank_win", "rank_sort_nt", "rank_sort_small")

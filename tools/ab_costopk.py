@@ -113,5 +113,5 @@ for k in args.k:
                     for e in prof.key_averages()
                     if "k_cos_t" in e.key or "k_cos_topk_merge" in e.key]
             for key, cnt, us in rows:
-                stage = "stage 2 k_cos_topk_merge" if "merge" in key else "stage 1 k_cos_t<3, 1, 1, 4>"
+                stage = "stage 2 k_cos_topk_merge" if "merge" in key else "stage 1 k_cos_t<kCosTopk>"
                 print(f"hint {hint}: {stage:<28} {cnt} launch(es), {us * 1e-3:9.3f} ms in all", flush=True)

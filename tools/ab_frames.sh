@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B the S7 MFMA cosine: each argument is a bench --option list ("-" = defaults), e.g. cos_kernel=3
+# A/B the S7 MFMA cosine: each argument is a bench --option list ("-" = defaults), e.g. cos_topk_hint=0
 for v in "$@"; do
   opts=""
   if [ "$v" != "-" ]; then for o in ${v//,/ }; do opts="$opts --option $o"; done; fi
